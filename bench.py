@@ -3,6 +3,13 @@
 resident in HBM, on N GPUs (one process per GPU).
 
     python bench.py [--gpus N --steps K --warmup W --rows R --groups G]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the frame, warms
+up, times K steps, writes the last step's result under DIR if
+--dump-outputs is given, and prints the JSON line.  `--full` adds every
+other leg to that line (CPU baselines, vwap, std, nulls, keys, many_groups,
+filter, sort, join, plugin; each can be dropped again with its --no-* flag).
 
 One step = one full query `filter(close > 250).group_by(symbol).agg(
 open.sum(), high.sum(), low.sum(), close.sum())` through the C-ABI.  With
@@ -35,6 +42,8 @@ METRIC = "Mrows/sec filter+groupby-agg on 1e9-row f64/i64; achieved HBM GB/s vs 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md chip table (spec)
 THRESHOLD = 250.0
 BYTES_PER_ROW = 8 + 4 * 8      # key + open/high/low/close read once (close is also the predicate)
+LEGS = ("cpu", "plugin", "vwap", "std", "sort", "join", "keys", "nulls", "filter", "many_groups")  # behind --full
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs writes at most this much
 
 
 def progress(msg: str) -> None:
@@ -51,6 +60,10 @@ def parse():
     ap.add_argument("--rows", type=float, default=None,
                     help="rows per GPU (default 1e9; 1.25e9 at 8 GPUs = configs[4]'s 1e10 rows)")
     ap.add_argument("--groups", type=int, default=100, help="distinct symbols (h2oai id4: K=100)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<column>.npy (float64, rows in ascending key order)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and every other leg; the --no-* flags drop legs from it")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="cpu_baseline time budget")
     ap.add_argument("--cpu-rows", type=float, default=1e7, help="cpu_baseline sample rows (configs[0]: 1e7)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -70,7 +83,28 @@ def parse():
     ap.add_argument("--leg-steps", type=int, default=5, help="timed steps of the sort and join legs (<= --steps)")
     ap.add_argument("--dry-run", action="store_true",
                     help="print this rank's launch parameters and exit before touching the GPU (tests)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run is the headline alone
+        for leg in LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+def dump_outputs(out, key: str, path: str) -> None:
+    """Write the frame a caller of the timed step received as
+    path/<column>.npy, float64.  group_by without maintain_order leaves the
+    group order unspecified, so the rows are written in ascending key order:
+    two builds given the same arguments then write comparable files.  Above
+    DUMP_MAX_BYTES in all, a fixed seeded sample of the (ordered) rows."""
+    os.makedirs(path, exist_ok=True)
+    cols = {c: out[c].to_numpy() for c in out.columns}
+    order = np.argsort(cols[key], kind="stable")
+    keep = DUMP_MAX_BYTES // (8 * len(cols))
+    if order.size > keep:
+        order = order[np.sort(np.random.default_rng(0).choice(order.size, keep, replace=False))]
+    for c, a in cols.items():
+        np.save(os.path.join(path, c + ".npy"), a[order].astype(np.float64))
 
 
 def make_data(torch, n: int, groups: int, seed: int):
@@ -893,6 +927,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     total_rows = n * world
     progress(f"headline: {ms_per_step:.3f} ms per step")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, "symbol", args.dump_outputs)
     value = total_rows * args.steps / dt / 1e6
     kms = float(np.mean(kernel_ms))
     achieved = BYTES_PER_ROW * n / (kms * 1e-3) / 1e9

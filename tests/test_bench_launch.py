@@ -45,6 +45,12 @@ def test_gpus_1_is_one_plain_process():
     assert lines == [{"rank": 0, "local_rank": 0, "world": 1, "rows_per_gpu": 1e9, "master_addr": None}]
 
 
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--dump-outputs", "unused", "--dry-run"])
+    assert r.returncode == 0, r.stderr
+    assert not os.path.exists("unused")
+
+
 def test_world_size_mismatch_is_refused():
     env = _env()
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")

@@ -12,6 +12,8 @@
 set -o pipefail
 TAG=${1:-run}; shift
 ARGS=${@:---steps 20 --warmup 5}
+# every leg of the line is cross-checked (tools/bench_evidence.py): they run under --full
+ARGS="--full $ARGS"
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/$TAG
