@@ -299,6 +299,11 @@ int plgpu_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
  *                  SIMD (off: measured slower)
  *   "srt_up_tiles" tiles per sort upsweep workgroup (1; more measured slower)
  *   "part_rows4"   1: 512-thread partition workgroups take 4 rows per thread
+ *   "over_presorted" 1: a caller that plgpu_segment_starts tells the keys
+ *                  arrive sorted runs its window expression over groups with
+ *                  no sort and no gather; 0: it sorts all the same (same
+ *                  results).  Read by the caller choosing the path (the host
+ *                  mirror's over()); the entry points do not depend on it
  * An unknown name is PLGPU_ERR_INVALID. */
 int plgpu_set_option(const char* name, int64_t value);
 int plgpu_get_option(const char* name, int64_t* out);
@@ -802,6 +807,41 @@ enum plgpu_rolling_kind {
 
 int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t window_size,
                   int64_t min_periods, int32_t center, plgpu_column* out, void* stream);
+
+/* ---- window expressions over groups (Expr.over) ------------------------------
+ * The device side of polars-expr/src/expressions/window.rs (WindowExpr::evaluate
+ * :356 with WindowMapping::GroupsToRows, determine_map_strategy :296) for
+ * rolling functions: the function runs on each group's rows in their order
+ * and every result goes back to its row.
+ *
+ * plgpu_segment_starts: one pass over 1..8 key columns (integer, float or
+ * Boolean; short String / Categorical keys as their Int64 / UInt32 codes).
+ * out_starts is a null-free Boolean column of n rows (library-owned), bit i
+ * set when i == 0 or row i's key tuple differs from row i - 1's -- the
+ * group-by's equality (TotalEq: -0.0 == 0.0, NaN == NaN; a null equals a null
+ * and nothing else).  *out_sorted = 1 when the rows are already non-decreasing
+ * in the order plgpu_arg_sort_multi gives with every column ascending and
+ * nulls first, so every run of equal tuples is a whole group (replaces
+ * window.rs:433 df.group_by_with_series for keys that arrive sorted).
+ *
+ * plgpu_rolling_segmented: plgpu_rolling (same kinds, ddof bits, dtypes, output
+ * dtype and validity rules) with every window also clipped to the segment of
+ * its own row, [last set bit of seg_starts at or before the row, next set bit
+ * after it): a row's output is bit-identical to plgpu_rolling's for that row
+ * over the segment alone as a column.  seg_starts: null-free Boolean column of
+ * the values' length (replaces window.rs:500 run_aggregation of a rolling
+ * function: its evaluation on every group's rows).
+ *
+ * plgpu_invert_permutation: out_idx[idx[j]] = j for a null-free UInt32 index
+ * column holding a permutation of 0..n-1 (as plgpu_arg_sort_multi returns), so
+ * sorted-order results go back to row order through plgpu_gather (replaces
+ * window.rs:125 map_by_arg_sort, the MapStrategy::Map branch at :524). */
+int plgpu_segment_starts(const plgpu_column* keys, int32_t nkeys, plgpu_column* out_starts,
+                         int32_t* out_sorted, void* stream);
+int plgpu_rolling_segmented(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind,
+                            int64_t window_size, int64_t min_periods, int32_t center,
+                            plgpu_column* out, void* stream);
+int plgpu_invert_permutation(const plgpu_column* idx, plgpu_column* out_idx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -189,6 +189,9 @@ SIGNATURES = {
     "plgpu_arg_sort_multi": (C.c_int, [_COLP, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _COLP, _P]),
     "plgpu_arg_sort": (C.c_int, [_COLP, C.c_int32, C.c_int32, _COLP, _P]),
     "plgpu_rolling": (C.c_int, [_COLP, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _COLP, _P]),
+    "plgpu_segment_starts": (C.c_int, [_COLP, C.c_int32, _COLP, C.POINTER(C.c_int32), _P]),
+    "plgpu_rolling_segmented": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _COLP, _P]),
+    "plgpu_invert_permutation": (C.c_int, [_COLP, _COLP, _P]),
 }
 
 GB_MAX_ACC = 6
@@ -299,6 +302,13 @@ def set_option(name: str, value: int) -> int:
     check(lib().plgpu_get_option(name.encode(), C.byref(prev)))
     check(lib().plgpu_set_option(name.encode(), int(value)))
     return int(prev.value)
+
+
+def get_option(name: str) -> int:
+    """A library option's current value (plgpu_get_option)."""
+    v = C.c_int64(0)
+    check(lib().plgpu_get_option(name.encode(), C.byref(v)))
+    return int(v.value)
 
 
 def release_cached() -> None:

@@ -82,6 +82,9 @@ struct Options {
     int join_radix_keys = 0;  // build keys per partition target (0: 2^15)
     int join_radix_load = 0;  // sub-table load factor in percent (0: 35)
     int join_radix_batch = 0; // match pass: probe steps with bucket reads in flight together, 4 or 8 (0: 4)
+    // window expressions over groups: 1 plgpu_segment_starts reports keys it finds sorted (no sort, no
+    // gather in Expr.over), 0 it never does, so every over() takes the sort path (tests / A-B)
+    int over_presorted = 1;
 };
 Options& options();
 

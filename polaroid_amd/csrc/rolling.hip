@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "plgpu_internal.hpp"
 #include "scan.hpp"
@@ -59,6 +60,78 @@ struct RlParams {
     uint32_t* rest;       // rl_var_hot_kernel: blocks for rl_var_rest_kernel (word 0: count)
 };
 
+// ---------------------------------------------------------------- segments
+// plgpu_rolling_segmented: a window is clipped to the segment of its own
+// row, [last set bit at or before the row, next set bit after it).  The
+// kernels take a compile-time SEG; the instantiations without it are the
+// ones plgpu_rolling launches: they take RlParams as before, the segmented
+// ones RlSegParams (RlP<SEG>), which the shared device code reaches through
+// its `const RlParams&` by a downcast under SEG.
+struct RlSegParams : RlParams {
+    const uint64_t* seg;  // the segment-start bitmap, bit i = row i starts a segment
+    int64_t seg_bytes;    // its length in bytes, ceil(n / 8)
+};
+template <bool SEG>
+using RlP = typename std::conditional<SEG, RlSegParams, RlParams>::type;
+
+__device__ __forceinline__ uint64_t seg_word(const uint64_t* seg, int64_t nbytes, int64_t wi) {
+    if ((wi + 1) * 8 <= nbytes) return seg[wi];
+    uint64_t v = 0;  // the last, partial word byte by byte (a caller's bitmap need not be padded)
+    const uint8_t* b = (const uint8_t*)seg;
+    for (int64_t j = wi * 8; j < nbytes; ++j) v |= (uint64_t)b[j] << (8 * (j - wi * 8));
+    return v;
+}
+
+// The last segment start at or before row i, looking no further back than
+// row lo (<= i): lo when there is none after it.
+__device__ __forceinline__ int64_t seg_prev(const uint64_t* seg, int64_t nbytes, int64_t i, int64_t lo) {
+    int64_t wi = i >> 6;
+    uint64_t m = seg_word(seg, nbytes, wi) & (~0ull >> (63 - (int)(i & 63)));
+    for (;;) {
+        if (m) {
+            const int64_t r = (wi << 6) + 63 - __clzll(m);
+            return r > lo ? r : lo;
+        }
+        if ((wi << 6) <= lo) return lo;
+        --wi;
+        m = seg_word(seg, nbytes, wi);
+    }
+}
+
+// The first segment start in (i, hi): hi when there is none (hi <= n).
+__device__ __forceinline__ int64_t seg_next(const uint64_t* seg, int64_t nbytes, int64_t i, int64_t hi) {
+    const int64_t q = i + 1;
+    if (q >= hi) return hi;
+    int64_t wi = q >> 6;
+    uint64_t m = seg_word(seg, nbytes, wi) & (~0ull << (int)(q & 63));
+    for (;;) {
+        if (m) {
+            const int64_t r = (wi << 6) + __builtin_ctzll(m);
+            return r < hi ? r : hi;
+        }
+        ++wi;
+        if ((wi << 6) >= hi) return hi;
+        m = seg_word(seg, nbytes, wi);
+    }
+}
+
+// Wave-uniform: is a segment start among rows (a, b)?  (b - a <= 64 * 63.)
+// Lane k tests word (a + 1) / 64 + k.
+__device__ __forceinline__ bool seg_any(const uint64_t* seg, int64_t nbytes, int64_t a, int64_t b) {
+    const int64_t q = a + 1;
+    bool hit = false;
+    if (q < b) {
+        const int64_t wi = (q >> 6) + (threadIdx.x & 63);
+        if ((wi << 6) < b) {
+            uint64_t m = seg_word(seg, nbytes, wi);
+            if ((wi << 6) < q) m &= ~0ull << (int)(q & 63);
+            if (b - (wi << 6) < 64) m &= ~(~0ull << (int)(b - (wi << 6)));
+            hit = m != 0;
+        }
+    }
+    return __ballot(hit) != 0;
+}
+
 // RN(a / w) for a full window (count w) without a division: q0 = RN(a y),
 // the exact remainder r = a - w q0 (one fma), q = RN(q0 + r y) with y =
 // RN(1 / w) -- correctly rounded for every a and w whose quotient and
@@ -81,6 +154,7 @@ __device__ __forceinline__ double rv_std(const RlParams& p, double v) {
     return __builtin_sqrt(p.var_f32 ? (double)(float)v : v);
 }
 
+template <bool SEG = false>
 __device__ __forceinline__ void rl_bounds(const RlParams& p, int64_t i, int64_t& s, int64_t& e) {
     if (p.center) {
         const int64_t right = (p.w + 1) / 2;
@@ -90,6 +164,13 @@ __device__ __forceinline__ void rl_bounds(const RlParams& p, int64_t i, int64_t&
     } else {
         s = i + 1 > p.w ? i + 1 - p.w : 0;
         e = i + 1;
+    }
+    if constexpr (SEG) {
+        if (i < p.n) {  // (a lane past the column keeps its unclipped bounds; it writes nothing)
+            const RlSegParams& sp = static_cast<const RlSegParams&>(p);
+            s = seg_prev(sp.seg, sp.seg_bytes, i, s);
+            e = seg_next(sp.seg, sp.seg_bytes, i, e);
+        }
     }
 }
 
@@ -187,8 +268,8 @@ __device__ __forceinline__ void rl_write(const RlParams& p, int64_t i, double su
 }
 
 // One workgroup = kRlOut outputs; ELEMS = LDS stage size.
-template <int ELEMS>
-__global__ __launch_bounds__(kRlThreads) void rl_tile_kernel(RlParams p) {
+template <int ELEMS, bool SEG = false>
+__global__ __launch_bounds__(kRlThreads) void rl_tile_kernel(RlP<SEG> p) {
     constexpr int PER = ELEMS / kRlThreads;
     __shared__ uint64_t L0[ELEMS], L1[ELEMS], L2[ELEMS];  // wrapping prefix sums
     __shared__ uint64_t CN[ELEMS];
@@ -229,7 +310,7 @@ __global__ __launch_bounds__(kRlThreads) void rl_tile_kernel(RlParams p) {
         // values too far apart for one window: exact per-output summation
         for (int64_t i = o0 + tid; i < o1; i += kRlThreads) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             RlCounts k = {0, 0, 0, 0};
             for (int64_t r = s; r < e; ++r) rl_count(p, r, k);
             bool valid;
@@ -300,7 +381,7 @@ __global__ __launch_bounds__(kRlThreads) void rl_tile_kernel(RlParams p) {
         bool valid = false;
         if (i < o1) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             const int je = (int)(e - lo) - 1, js = (int)(s - lo) - 1;
             uint64_t s0 = 0, s1 = 0, s2 = 0, cnt = 0;
             if (je >= 0) {
@@ -461,16 +542,20 @@ __device__ __forceinline__ uint64_t rw_load(const RlParams& p, int64_t r, bool t
 // non-finite value, so non-null / inf / NaN counts are scanned too (else a
 // window's non-null count is its length).  Straight-line per chunk: every
 // branch below is uniform and resolved at compile time or once per wave.
-template <int MODE, bool COUNTS, bool MEAN>
+// SEG / clip: a segment start lies among the block's rows, so every window
+// takes its bounds from rl_bounds<SEG> (the ring reads stay inside the
+// block's rows: clipping only narrows a window).
+template <int MODE, bool COUNTS, bool MEAN, bool SEG = false>
 __device__ __forceinline__ void rw_scan(const RlParams& p, const uint64_t (&x)[kRwChunks + 1],
                                         const uint64_t (&vm)[kRwChunks + 1], int64_t o_first, int64_t o_end,
-                                        int64_t s_first, int tmin, uint64_t* rlo, uint64_t* rhi, uint64_t* rcn) {
+                                        int64_t s_first, int tmin, uint64_t* rlo, uint64_t* rhi, uint64_t* rcn,
+                                        bool clip = false) {
     const int lane = threadIdx.x & 63;
     const int bottom = tmin - 1075;
     // interior waves: every window is unclipped, [i - left, i + right)
     const int64_t right = p.center ? (p.w + 1) / 2 : 1;
     const int64_t left = p.w - right;
-    const bool interior = o_first - left >= 0 && o_end + right - 1 <= p.n;
+    const bool interior = o_first - left >= 0 && o_end + right - 1 <= p.n && !(SEG && clip);
     uint64_t carry_lo = 0, carry_hi = 0, carry_cn = 0;
 #pragma unroll
     for (int k = 0; k <= kRwChunks; ++k) {
@@ -532,7 +617,7 @@ __device__ __forceinline__ void rw_scan(const RlParams& p, const uint64_t (&x)[k
             s = i - left;
             e = i + right;
         } else {
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
         }
         const int je = (int)(e - 1 - s_first), js = (int)(s - 1 - s_first);
         const int ie = je & (kRwRing - 1), is = js & (kRwRing - 1);
@@ -646,7 +731,8 @@ __device__ __forceinline__ void rw_scan_full(const RlParams& p, const uint64_t (
 // A wave's outputs summed exactly one by one (values spanning more binades
 // than 128 bits hold).  Out of line, with its own copy of the parameters, so
 // the kernel's parameters never have their address taken.
-__device__ __noinline__ void rw_exact_outputs(RlParams p, int64_t o_first, int64_t o_end) {
+template <bool SEG = false>
+__device__ __noinline__ void rw_exact_outputs(RlP<SEG> p, int64_t o_first, int64_t o_end) {
     const int lane = threadIdx.x & 63;
     for (int q = 0; q < kRwChunks; ++q) {
         const int64_t i = o_first + 64 * q + lane;
@@ -654,7 +740,7 @@ __device__ __noinline__ void rw_exact_outputs(RlParams p, int64_t o_first, int64
         bool valid = false;
         if (i < o_end) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             RlCounts k = {0, 0, 0, 0};
             for (int64_t r = s; r < e; ++r) rl_count(p, r, k);
             rl_write(p, i, rl_exact_sum(p, s, e), 0, k, e - s, valid);
@@ -769,7 +855,8 @@ __device__ double rv_window_exact(const RlParams& p, int64_t s, int64_t e, int64
 
 // A wave's outputs one by one, exactly (out of line: its big integers live
 // in private memory; only waves whose values the fast form cannot hold).
-__device__ __noinline__ void rw_var_exact_outputs(RlParams p, int64_t o_first, int64_t o_end) {
+template <bool SEG = false>
+__device__ __noinline__ void rw_var_exact_outputs(RlP<SEG> p, int64_t o_first, int64_t o_end) {
     const int lane = threadIdx.x & 63;
     for (int q = 0; q < kRwChunks; ++q) {
         const int64_t i = o_first + 64 * q + lane;
@@ -777,7 +864,7 @@ __device__ __noinline__ void rw_var_exact_outputs(RlParams p, int64_t o_first, i
         bool valid = false;
         if (i < o_end) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             RlCounts k = {0, 0, 0, 0};
             for (int64_t r = s; r < e; ++r) rl_count(p, r, k);
             valid = k.nn >= p.min_periods && k.nn > p.ddof;
@@ -822,16 +909,16 @@ __device__ __forceinline__ double u192_to_double(uint64_t w0, uint64_t w1, uint6
 // Scan + emit of the fast form: prefix sums of t (int64), t^2 (128-bit)
 // and, with COUNTS, the non-null / inf / NaN counts; per output the exact
 // window sums S1, S2 give num = c * S2 - S1^2 (192-bit, exact).
-template <bool COUNTS>
+template <bool COUNTS, bool SEG = false>
 __device__ __forceinline__ void rw_var_scan(const RlParams& p, const uint64_t (&x)[kRwChunks + 1],
                                             const uint64_t (&vm)[kRwChunks + 1], int64_t o_first, int64_t o_end,
                                             int64_t s_first, int tmin, uint64_t* r1, uint64_t* r2l, uint64_t* r2h,
-                                            uint64_t* rcn) {
+                                            uint64_t* rcn, bool clip = false) {
     const int lane = threadIdx.x & 63;
     const int bottom = tmin - 1075;
     const int64_t right = p.center ? (p.w + 1) / 2 : 1;
     const int64_t left = p.w - right;
-    const bool interior = o_first - left >= 0 && o_end + right - 1 <= p.n;
+    const bool interior = o_first - left >= 0 && o_end + right - 1 <= p.n && !(SEG && clip);
     uint64_t c1 = 0, c2l = 0, c2h = 0, ccn = 0;
 #pragma unroll
     for (int k = 0; k <= kRwChunks; ++k) {
@@ -877,7 +964,7 @@ __device__ __forceinline__ void rw_var_scan(const RlParams& p, const uint64_t (&
             s = i - left;
             e = i + right;
         } else {
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
         }
         const int je = (int)(e - 1 - s_first), js = (int)(s - 1 - s_first);
         const int ie = je & (kRwRing - 1), is = js & (kRwRing - 1);
@@ -1076,10 +1163,22 @@ __device__ __forceinline__ void rw_load_block(const RlParams& p, int64_t s_first
 
 // One wave's block of kRwOut outputs from its loaded rows: validity, the
 // exponent range and the number format, then the scan + emit.
-template <int DT, bool NULLABLE, bool VAR>
+// Segmented kernels: does a segment start lie after the first row the block's
+// windows reach (s_first, the unclipped start of its first output's window)
+// and before their end?  Without one every window of the block is whole and
+// the block runs as in plgpu_rolling (a start at s_first itself, or before
+// it, clips nothing: no window of the block begins earlier).
+__device__ __forceinline__ bool rw_block_clipped(const RlParams& p, int64_t o_first, int64_t s_first) {
+    const int64_t right = p.center ? (p.w + 1) / 2 : 1;
+    const int64_t end = o_first + kRwOut + right - 1;
+    const RlSegParams& sp = static_cast<const RlSegParams&>(p);
+    return seg_any(sp.seg, sp.seg_bytes, s_first, end < p.n ? end : p.n);
+}
+
+template <int DT, bool NULLABLE, bool VAR, bool SEG = false>
 __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChunks + 1], int64_t o_first,
                                          int64_t s_first, uint64_t* rlo, uint64_t* rhi, uint64_t* rcn,
-                                         uint64_t* rv2) {
+                                         uint64_t* rv2, bool clip = false) {
     const int lane = threadIdx.x & 63;
     const int64_t o_end = o_first + kRwOut < p.n ? o_first + kRwOut : p.n;
     const bool isint = p.out_int != 0;  // (var / std: integers enter as their f64 values)
@@ -1108,8 +1207,9 @@ __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChu
     const bool counts = __ballot(odd) != 0;
     if (isint) {
         // (the exponent fields of integers mean nothing; only nulls count)
-        if (__ballot(NULLABLE && odd) != 0) rw_scan<0, true, false>(p, x, vm, o_first, o_end, s_first, 0, rlo, rhi, rcn);
-        else rw_scan<0, false, false>(p, x, vm, o_first, o_end, s_first, 0, rlo, rhi, rcn);
+        if (__ballot(NULLABLE && odd) != 0)
+            rw_scan<0, true, false, SEG>(p, x, vm, o_first, o_end, s_first, 0, rlo, rhi, rcn, clip);
+        else rw_scan<0, false, false, SEG>(p, x, vm, o_first, o_end, s_first, 0, rlo, rhi, rcn, clip);
         return;
     }
 #pragma unroll
@@ -1127,11 +1227,11 @@ __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChu
         // sums in 127 bits, and no result near the subnormal range
         const bool vfast = mx == 0 || (tmin >= 600 && lw + 53 + span <= 63 && 2 * (53 + span) + lw <= 126);
         if (!vfast) {
-            rw_var_exact_outputs(p, o_first, o_end);
+            rw_var_exact_outputs<SEG>(static_cast<const RlP<SEG>&>(p), o_first, o_end);
             return;
         }
         const int64_t right = p.center ? (p.w + 1) / 2 : 1;
-        if (!counts && p.full && o_first - (p.w - right) >= 0 && o_end + right - 1 <= p.n) {
+        if (!counts && p.full && !(SEG && clip) && o_first - (p.w - right) >= 0 && o_end + right - 1 <= p.n) {
             // nonzero numerators lie in [2^(2 bottom), 2^(2 (tmax - 1022) + 2 lw)):
             // both quotients inside rw_div's exponent range
             const int b2 = 2 * (tmin - 1075), top = 2 * (tmax - 1022) + 2 * lw;
@@ -1142,17 +1242,17 @@ __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChu
             else rw_var_scan_full<false, false>(p, x, o_first, o_end, s_first, tmin, rlo);
             return;
         }
-        if (counts) rw_var_scan<true>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rv2, rcn);
-        else rw_var_scan<false>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rv2, rcn);
+        if (counts) rw_var_scan<true, SEG>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rv2, rcn, clip);
+        else rw_var_scan<false, SEG>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rv2, rcn, clip);
         return;
     }
     // int64 when any window's sum fits 63 bits and results cannot be subnormal
     const bool narrow = mx == 0 || (tmin >= 128 && lw + 53 + span <= 63);
     if (!narrow && lw + 53 + span > 127) {
-        rw_exact_outputs(p, o_first, o_end);  // beyond 128 bits
+        rw_exact_outputs<SEG>(static_cast<const RlP<SEG>&>(p), o_first, o_end);  // beyond 128 bits
         return;
     }
-    if (narrow && !counts && p.full) {
+    if (narrow && !counts && p.full && !(SEG && clip)) {
         const int64_t right = p.center ? (p.w + 1) / 2 : 1;
         if (o_first - (p.w - right) >= 0 && o_end + right - 1 <= p.n) {
             // the one-correction mean without its per-lane test: nonzero
@@ -1165,8 +1265,8 @@ __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChu
         }
     }
 #define PLGPU_RW(M, C)                                                                                   \
-    (p.mean ? rw_scan<M, C, true>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rcn)               \
-            : rw_scan<M, C, false>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rcn))
+    (p.mean ? rw_scan<M, C, true, SEG>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rcn, clip)    \
+            : rw_scan<M, C, false, SEG>(p, x, vm, o_first, o_end, s_first, tmin, rlo, rhi, rcn, clip))
     if (narrow) {
         if (counts) PLGPU_RW(1, true);
         else PLGPU_RW(1, false);
@@ -1180,8 +1280,8 @@ __device__ __forceinline__ void rw_block(const RlParams& p, uint64_t (&x)[kRwChu
 // One block of kRwOut outputs per wave.  (A register cap for 6 waves per
 // SIMD, __launch_bounds__(256, 6), spilled 6 VGPRs and still ended at 5
 // waves: not kept.)
-template <int DT, bool NULLABLE, bool VAR = false>
-__global__ __launch_bounds__(256) void rl_wave_kernel(RlParams p) {
+template <int DT, bool NULLABLE, bool VAR = false, bool SEG = false>
+__global__ __launch_bounds__(256) void rl_wave_kernel(RlP<SEG> p) {
     // each wave's three rings, adjacent (rw_scan_full uses them as one array)
     __shared__ uint64_t ring[kRwWaves][3 * kRwRing];
     __shared__ uint64_t ring_v2[VAR ? kRwWaves : 1][VAR ? kRwRing : 1];  // var: the t^2 prefixes' high words
@@ -1192,8 +1292,10 @@ __global__ __launch_bounds__(256) void rl_wave_kernel(RlParams p) {
     rl_bounds(p, o_first, s_first, tmp);
     uint64_t x[kRwChunks + 1];
     rw_load_block<DT>(p, s_first, x);
-    rw_block<DT, NULLABLE, VAR>(p, x, o_first, s_first, ring[wv], ring[wv] + kRwRing, ring[wv] + 2 * kRwRing,
-                                VAR ? ring_v2[wv] : nullptr);
+    bool clip = false;
+    if constexpr (SEG) clip = rw_block_clipped(p, o_first, s_first);
+    rw_block<DT, NULLABLE, VAR, SEG>(p, x, o_first, s_first, ring[wv], ring[wv] + kRwRing, ring[wv] + 2 * kRwRing,
+                                     VAR ? ring_v2[wv] : nullptr, clip);
 }
 
 // Resident waves, each over blocks b, b + stride, ...: the next block's
@@ -1313,8 +1415,8 @@ __device__ __forceinline__ bool rw_mean_hot_block(const RlParams& p, uint64_t (&
     return true;
 }
 
-template <int DT>
-__global__ __launch_bounds__(256) void rl_mean_hot_kernel(RlParams p) {
+template <int DT, bool SEG = false>
+__global__ __launch_bounds__(256) void rl_mean_hot_kernel(RlP<SEG> p) {
     __shared__ uint64_t ring[kRwWaves][kRwChunks * 64 + 64 + 1];  // rw_scan_full's prefixes
     const int wv = threadIdx.x >> 6;
     const int64_t nblocks = (p.n + kRwOut - 1) / kRwOut;
@@ -1327,12 +1429,14 @@ __global__ __launch_bounds__(256) void rl_mean_hot_kernel(RlParams p) {
     rl_bounds(p, b * kRwOut, s_first, tmp);
     uint64_t x[kRwChunks + 1];
     rw_load_block<DT>(p, s_first, x);
-    if (!rw_mean_hot_block<DT>(p, x, b * kRwOut, s_first, ring[wv], lw, right) && (threadIdx.x & 63) == 0)
+    bool clip = false;  // a block with a segment start in reach goes to the rest list
+    if constexpr (SEG) clip = rw_block_clipped(p, b * kRwOut, s_first);
+    if ((clip || !rw_mean_hot_block<DT>(p, x, b * kRwOut, s_first, ring[wv], lw, right)) && (threadIdx.x & 63) == 0)
         p.rest[1 + atomicAdd(&p.rest[0], 1u)] = (uint32_t)b;
 }
 
-template <int DT, bool STREAM, bool STD>
-__global__ __launch_bounds__(256) void rl_var_hot_kernel(RlParams p) {
+template <int DT, bool STREAM, bool STD, bool SEG = false>
+__global__ __launch_bounds__(256) void rl_var_hot_kernel(RlP<SEG> p) {
     __shared__ uint64_t ring[kRwWaves][3 * kRwRing];
     const int wv = threadIdx.x >> 6;
     const int64_t nblocks = (p.n + kRwOut - 1) / kRwOut;
@@ -1358,7 +1462,10 @@ __global__ __launch_bounds__(256) void rl_var_hot_kernel(RlParams p) {
                 rw_load_block<DT>(p, sn, xn);
             }
         }
-        if (!rw_var_hot_block<DT, STD>(p, x, b * kRwOut, s_first, ring[wv], lw, right) && (threadIdx.x & 63) == 0)
+        bool clip = false;
+        if constexpr (SEG) clip = rw_block_clipped(p, b * kRwOut, s_first);
+        if ((clip || !rw_var_hot_block<DT, STD>(p, x, b * kRwOut, s_first, ring[wv], lw, right)) &&
+            (threadIdx.x & 63) == 0)
             p.rest[1 + atomicAdd(&p.rest[0], 1u)] = (uint32_t)b;
         if constexpr (STREAM) {
 #pragma unroll
@@ -1369,8 +1476,8 @@ __global__ __launch_bounds__(256) void rl_var_hot_kernel(RlParams p) {
 }
 
 // The blocks rl_var_hot_kernel / rl_mean_hot_kernel left, one per wave, by rw_block.
-template <int DT, bool VAR = true>
-__global__ __launch_bounds__(256) void rl_var_rest_kernel(RlParams p) {
+template <int DT, bool VAR = true, bool SEG = false>
+__global__ __launch_bounds__(256) void rl_var_rest_kernel(RlP<SEG> p) {
     __shared__ uint64_t ring[kRwWaves][3 * kRwRing];
     __shared__ uint64_t ring_v2[VAR ? kRwWaves : 1][VAR ? kRwRing : 1];
     const int wv = threadIdx.x >> 6;
@@ -1381,20 +1488,23 @@ __global__ __launch_bounds__(256) void rl_var_rest_kernel(RlParams p) {
         rl_bounds(p, b * kRwOut, s_first, tmp);
         uint64_t x[kRwChunks + 1];
         rw_load_block<DT>(p, s_first, x);
-        rw_block<DT, false, VAR>(p, x, b * kRwOut, s_first, ring[wv], ring[wv] + kRwRing, ring[wv] + 2 * kRwRing,
-                                 VAR ? ring_v2[wv] : nullptr);
+        bool clip = false;
+        if constexpr (SEG) clip = rw_block_clipped(p, b * kRwOut, s_first);
+        rw_block<DT, false, VAR, SEG>(p, x, b * kRwOut, s_first, ring[wv], ring[wv] + kRwRing,
+                                      ring[wv] + 2 * kRwRing, VAR ? ring_v2[wv] : nullptr, clip);
     }
 }
 
 // rolling var / std over windows wider than the wave kernel's: each output
 // from its exact window sums (rv_window_exact; O(window) per output).
-__global__ void rl_direct_var_kernel(RlParams p) {
+template <bool SEG = false>
+__global__ void rl_direct_var_kernel(RlP<SEG> p) {
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p.n; base += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = base + threadIdx.x;
         bool valid = false;
         if (i < p.n) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             RlCounts k = {0, 0, 0, 0};
             for (int64_t r = s; r < e; ++r) rl_count(p, r, k);
             valid = k.nn >= p.min_periods && k.nn > p.ddof;
@@ -1411,13 +1521,14 @@ __global__ void rl_direct_var_kernel(RlParams p) {
 }
 
 // Windows too wide for the LDS stage: per-output direct summation.
-__global__ void rl_direct_kernel(RlParams p) {
+template <bool SEG = false>
+__global__ void rl_direct_kernel(RlP<SEG> p) {
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p.n; base += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = base + threadIdx.x;
         bool valid = false;
         if (i < p.n) {
             int64_t s, e;
-            rl_bounds(p, i, s, e);
+            rl_bounds<SEG>(p, i, s, e);
             RlCounts k = {0, 0, 0, 0};
             uint64_t isum = 0;
             for (int64_t r = s; r < e; ++r) {
@@ -1463,6 +1574,8 @@ struct MmParams {
     uint64_t* pre;           // van Herk prefix codes (or null)
     uint64_t* suf;           // van Herk suffix codes
     const uint64_t* vcount;  // exclusive prefix counts of valid rows (nulls only), n + 1
+    const uint64_t* seg;     // segmented kernels (SEG): the segment-start bitmap
+    int64_t seg_bytes;
 };
 
 __device__ __forceinline__ uint64_t mm_code(const MmParams& p, int64_t r) {
@@ -1479,6 +1592,7 @@ __device__ __forceinline__ uint64_t mm_best(const MmParams& p, uint64_t a, uint6
     return p.is_max ? (a > b ? a : b) : (a < b ? a : b);
 }
 
+template <bool SEG = false>
 __device__ __forceinline__ void mm_bounds(const MmParams& p, int64_t i, int64_t& s, int64_t& e) {
     if (p.center) {
         const int64_t right = (p.w + 1) / 2;
@@ -1488,6 +1602,10 @@ __device__ __forceinline__ void mm_bounds(const MmParams& p, int64_t i, int64_t&
     } else {
         s = i + 1 > p.w ? i + 1 - p.w : 0;
         e = i + 1;
+    }
+    if constexpr (SEG) {  // (callers pass i < n)
+        s = seg_prev(p.seg, p.seg_bytes, i, s);
+        e = seg_next(p.seg, p.seg_bytes, i, e);
     }
 }
 
@@ -1534,6 +1652,7 @@ __global__ __launch_bounds__(256) void mm_blocks_kernel(MmParams p) {
 // outputs' input span in LDS once (coalesced), then every output scans its
 // window there.
 constexpr int kMmTile = 1024;
+template <bool SEG = false>
 __global__ __launch_bounds__(256) void mm_direct_kernel(MmParams p) {
     __shared__ uint64_t codes[kMmTile + kMmDirect];
     const uint64_t ident = p.is_max ? 0ull : ~0ull;
@@ -1552,7 +1671,7 @@ __global__ __launch_bounds__(256) void mm_direct_kernel(MmParams p) {
             uint64_t v = 0;
             if (i < p.n) {
                 int64_t s, e;
-                mm_bounds(p, i, s, e);
+                mm_bounds<SEG>(p, i, s, e);
                 uint64_t best = ident;
                 for (int64_t r = s; r < e; ++r) best = mm_best(p, best, codes[r - lo]);
                 const int64_t cnt = p.vcount ? (int64_t)(p.vcount[e] - p.vcount[s]) : e - s;
@@ -1571,15 +1690,19 @@ __global__ __launch_bounds__(256) void mm_direct_kernel(MmParams p) {
     }
 }
 
+// SEG: the segmented form always scans its window (p.pre null): van Herk's
+// same-block case returns suf[s] alone, which is wrong for a window clipped
+// on both sides inside one block.
+template <bool SEG = false>
 __global__ __launch_bounds__(256) void mm_out_kernel(MmParams p) {
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < p.n; i0 += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = i0 + threadIdx.x;
         bool valid = false;
         if (i < p.n) {
             int64_t s, e;
-            mm_bounds(p, i, s, e);
+            mm_bounds<SEG>(p, i, s, e);
             uint64_t best;
-            if (p.pre) {
+            if (!SEG && p.pre) {
                 // [s, e) lies in one block, or spans two adjacent ones
                 best = (s / p.w == (e - 1) / p.w && s % p.w != 0) ? p.suf[s]
                        : (s % p.w == 0 ? p.pre[e - 1] : mm_best(p, p.suf[s], p.pre[e - 1]));
@@ -1607,10 +1730,12 @@ __global__ __launch_bounds__(256) void mm_valid_flags_kernel(DevCol c, int64_t n
         f[r] = dev_valid(c, r) ? 1 : 0;
 }
 
-static int rolling_minmax(const plgpu_column* values, bool is_max, int64_t w, int64_t min_periods, bool center,
-                          plgpu_column* out, hipStream_t s) {
+static int rolling_minmax(const plgpu_column* values, const uint64_t* seg, bool is_max, int64_t w,
+                          int64_t min_periods, bool center, plgpu_column* out, hipStream_t s) {
     MmParams p;
     std::memset(&p, 0, sizeof p);
+    p.seg = seg;
+    p.seg_bytes = (values->length + 7) / 8;
     p.c = dev_col(*values);
     p.n = values->length;
     p.w = w;
@@ -1639,7 +1764,12 @@ static int rolling_minmax(const plgpu_column* values, bool is_max, int64_t w, in
             p.vcount = vcount;
         }
     }
-    if (!rc && e == hipSuccess && w > kMmDirect) {
+    if (!rc && e == hipSuccess && seg != nullptr) {
+        KtScope kt("mm_seg_kernel", s);
+        if (w > kMmDirect) mm_out_kernel<true><<<g, 256, 0, s>>>(p);
+        else mm_direct_kernel<true><<<(unsigned)std::min<int64_t>((p.n + kMmTile - 1) / kMmTile, 256 * 64), 256, 0, s>>>(p);
+        e = hipGetLastError();
+    } else if (!rc && e == hipSuccess && w > kMmDirect) {
         rc = dev_alloc((void**)&p.pre, p.n * 8, s);
         if (!rc) rc = dev_alloc((void**)&p.suf, p.n * 8, s);
         if (!rc) {
@@ -1648,11 +1778,11 @@ static int rolling_minmax(const plgpu_column* values, bool is_max, int64_t w, in
             e = hipGetLastError();
         }
         if (!rc && e == hipSuccess) {
-            mm_out_kernel<<<g, 256, 0, s>>>(p);
+            mm_out_kernel<false><<<g, 256, 0, s>>>(p);
             e = hipGetLastError();
         }
     } else if (!rc && e == hipSuccess) {
-        mm_direct_kernel<<<(unsigned)std::min<int64_t>((p.n + kMmTile - 1) / kMmTile, 256 * 64), 256, 0, s>>>(p);
+        mm_direct_kernel<false><<<(unsigned)std::min<int64_t>((p.n + kMmTile - 1) / kMmTile, 256 * 64), 256, 0, s>>>(p);
         e = hipGetLastError();
     }
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1679,11 +1809,50 @@ static int num_cus_rl() {
     return n;
 }
 
-PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t window_size, int64_t min_periods,
-                            int32_t center, plgpu_column* out, void* stream) {
+// The segmented launches of the wave family (w <= kRwMaxW), per input dtype:
+// the hot / rest split where plgpu_rolling takes it, else one block per wave.
+template <int DT>
+static void rl_launch_seg(const RlSegParams& p, bool var, bool nl, bool hot, bool mhot, unsigned g, unsigned gr,
+                          hipStream_t s) {
+    if (mhot) {
+        rl_mean_hot_kernel<DT, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+        rl_var_rest_kernel<DT, false, true><<<gr, 64 * kRwWaves, 0, s>>>(p);
+    } else if (hot) {
+        if (p.var == 2) rl_var_hot_kernel<DT, false, true, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+        else rl_var_hot_kernel<DT, false, false, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+        rl_var_rest_kernel<DT, true, true><<<gr, 64 * kRwWaves, 0, s>>>(p);
+    } else if (var) {
+        if (nl) rl_wave_kernel<DT, true, true, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+        else rl_wave_kernel<DT, false, true, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+    } else {
+        if (nl) rl_wave_kernel<DT, true, false, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+        else rl_wave_kernel<DT, false, false, true><<<g, 64 * kRwWaves, 0, s>>>(p);
+    }
+}
+
+// Bits [off, off + n) of a bitmap as words from bit 0 (a segment-start
+// column with an offset or a values pointer that is not 8-byte aligned).
+__global__ __launch_bounds__(256) void seg_repack_kernel(DevCol c, int64_t n, uint64_t* __restrict__ out) {
+    const int64_t words = (n + 63) / 64;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < words * 64;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t m = __ballot(r < n && dev_load(c, r) != 0);
+        if ((threadIdx.x & 63) == 0) out[r >> 6] = m;
+    }
+}
+
+static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind,
+                        int64_t window_size, int64_t min_periods, int32_t center, plgpu_column* out, void* stream) {
     hipStream_t s = as_stream(stream);
     if (values == nullptr || out == nullptr) return fail(PLGPU_ERR_INVALID, "NULL argument");
     std::memset(out, 0, sizeof *out);
+    const bool segd = seg_starts != nullptr;
+    if (segd) {
+        if (seg_starts->dtype != PLGPU_BOOL) return fail(PLGPU_ERR_SCHEMA, "segment starts must be a Boolean column");
+        if (seg_starts->validity != nullptr) return fail(PLGPU_ERR_SCHEMA, "segment starts must not be nullable");
+        if (seg_starts->length != values->length)
+            return fail(PLGPU_ERR_SHAPE, "segment starts and values must have equal lengths");
+    }
     // bits 8..15: ddof; bit 16 (std of a Float32 column): the variance is
     // rounded to Float32 before the square root, as the reference's f32 sqrt
     const int32_t base = kind & 0xFF, ddof = (kind >> 8) & 0xFF, var_f32 = (kind >> 16) & 1;
@@ -1697,10 +1866,38 @@ PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t wi
     if (min_periods < 0) return fail(PLGPU_ERR_INVALID, "min_periods must be >= 0");
     if (min_periods > window_size)
         return fail(PLGPU_ERR_INVALID, "`min_periods` should be <= `window_size`");
-    if (kind == PLGPU_ROLLING_MIN || kind == PLGPU_ROLLING_MAX)
-        return rolling_minmax(values, kind == PLGPU_ROLLING_MAX, window_size, min_periods, center != 0, out, s);
-    RlParams p;
+    // the bitmap as 8-byte words from bit 0: the column's own buffer where
+    // it is laid out so (as plgpu_segment_starts writes it), else a copy
+    const uint64_t* seg = nullptr;
+    uint64_t* seg_own = nullptr;
+    if (segd && values->length > 0) {
+        const uintptr_t at = (uintptr_t)seg_starts->values + (uintptr_t)(seg_starts->offset / 8);
+        if (seg_starts->offset % 8 == 0 && at % 8 == 0) {
+            seg = (const uint64_t*)at;
+        } else {
+            const int64_t words = (values->length + 63) / 64;
+            int rc = dev_alloc((void**)&seg_own, (size_t)words * 8, s);
+            if (rc) return rc;
+            seg_repack_kernel<<<(unsigned)std::min<int64_t>((words * 64 + 255) / 256, 256 * 64), 256, 0, s>>>(
+                dev_col(*seg_starts), values->length, seg_own);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) {
+                dev_free(seg_own, s);
+                return hip_fail(e, "segment starts");
+            }
+            seg = seg_own;
+        }
+    }
+    if (kind == PLGPU_ROLLING_MIN || kind == PLGPU_ROLLING_MAX) {
+        const int rc = rolling_minmax(values, seg, kind == PLGPU_ROLLING_MAX, window_size, min_periods, center != 0,
+                                      out, s);
+        dev_free(seg_own, s);
+        return rc;
+    }
+    RlSegParams p;  // (the plain kernels take its RlParams part)
     std::memset(&p, 0, sizeof p);
+    p.seg = seg;
+    p.seg_bytes = (values->length + 7) / 8;
     p.c.dtype = values->dtype;
     p.c.offset = values->offset;
     p.c.values = values->values;
@@ -1724,14 +1921,18 @@ PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t wi
     p.out_int = (!p.mean && !var && !p.isf) ? values->dtype : 0;
     const int32_t odt = p.out_int ? values->dtype : PLGPU_F64;
     int rc = make_owned_column(out, odt, p.n, true, s);
-    if (rc || p.n == 0) return rc;
+    if (rc || p.n == 0) {
+        dev_free(seg_own, s);
+        return rc;
+    }
     p.out = (void*)out->values;
     p.out_valid = (uint64_t*)out->validity;
     const int64_t tiles = (p.n + kRlOut - 1) / kRlOut;
     if (window_size <= kRwMaxW) {
         const unsigned g = (unsigned)((p.n + (int64_t)kRwOut * kRwWaves - 1) / ((int64_t)kRwOut * kRwWaves));
         const bool nl = p.c.validity != nullptr;
-        KtScope kt(var ? "rl_wave_var_kernel" : "rl_wave_kernel", s);
+        KtScope kt(seg ? (var ? "rl_wave_var_seg_kernel" : "rl_wave_seg_kernel")
+                       : (var ? "rl_wave_var_kernel" : "rl_wave_kernel"), s);
         const bool hot = var && !nl && !p.var_f32 && options().rl_var_hot && p.full && p.fast_div && p.var128;
         const bool mhot = !var && !nl && !p.out_int && options().rl_mean_hot && p.full;
         if (hot || mhot) {
@@ -1742,6 +1943,7 @@ PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t wi
             if (!arc && hipMemsetAsync(p.rest, 0, 4, s) != hipSuccess) arc = PLGPU_ERR_HIP;
             if (arc) {
                 if (p.rest) dev_free(p.rest, s);
+                dev_free(seg_own, s);
                 plgpu_column_release(out);
                 return arc == PLGPU_ERR_HIP ? hip_fail(hipGetLastError(), "rolling") : arc;
             }
@@ -1762,10 +1964,18 @@ PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t wi
         else rl_var_hot_kernel<DT, false, false><<<g, 64 * kRwWaves, 0, s>>>(p);               \
         rl_var_rest_kernel<DT><<<gr, 64 * kRwWaves, 0, s>>>(p);              \
     } while (0)
-            if (values->dtype == PLGPU_F64) PLGPU_RLHOT(PLGPU_F64);
+            if (seg) {
+                if (values->dtype == PLGPU_F64) rl_launch_seg<PLGPU_F64>(p, var, nl, hot, mhot, g, gr, s);
+                else if (values->dtype == PLGPU_I64) rl_launch_seg<PLGPU_I64>(p, var, nl, hot, mhot, g, gr, s);
+                else rl_launch_seg<PLGPU_I32>(p, var, nl, hot, mhot, g, gr, s);
+            } else if (values->dtype == PLGPU_F64) PLGPU_RLHOT(PLGPU_F64);
             else if (values->dtype == PLGPU_I64) PLGPU_RLHOT(PLGPU_I64);
             else PLGPU_RLHOT(PLGPU_I32);
 #undef PLGPU_RLHOT
+        } else if (seg) {
+            if (values->dtype == PLGPU_F64) rl_launch_seg<PLGPU_F64>(p, var, nl, false, false, g, 1, s);
+            else if (values->dtype == PLGPU_I64) rl_launch_seg<PLGPU_I64>(p, var, nl, false, false, g, 1, s);
+            else rl_launch_seg<PLGPU_I32>(p, var, nl, false, false, g, 1, s);
         } else if (!nl && options().rl_stream != 0) {
             // null-free: resident waves streaming their blocks
             const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
@@ -1801,21 +2011,41 @@ PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t wi
             if (nl) rl_wave_kernel<PLGPU_I32, true><<<g, 64 * kRwWaves, 0, s>>>(p);
             else rl_wave_kernel<PLGPU_I32, false><<<g, 64 * kRwWaves, 0, s>>>(p);
         }
+    } else if (seg) {
+        // wider windows, segmented: the same kernels with clipped bounds
+        KtScope kt(var ? "rl_wide_var_seg_kernel" : "rl_wide_seg_kernel", s);
+        if (var) rl_direct_var_kernel<true><<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
+        else if (window_size - 1 + kRlOut <= 2048) rl_tile_kernel<2048, true><<<(unsigned)tiles, kRlThreads, 0, s>>>(p);
+        else if (window_size - 1 + kRlOut <= 4096) rl_tile_kernel<4096, true><<<(unsigned)tiles, kRlThreads, 0, s>>>(p);
+        else rl_direct_kernel<true><<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
     } else if (var)
-        rl_direct_var_kernel<<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
+        rl_direct_var_kernel<false><<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
     else if (window_size - 1 + kRlOut <= 2048)
         rl_tile_kernel<2048><<<(unsigned)tiles, kRlThreads, 0, s>>>(p);
     else if (window_size - 1 + kRlOut <= 4096)
         rl_tile_kernel<4096><<<(unsigned)tiles, kRlThreads, 0, s>>>(p);
     else
-        rl_direct_kernel<<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
+        rl_direct_kernel<false><<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (p.rest) dev_free(p.rest, s);
+    dev_free(seg_own, s);
     if (e != hipSuccess) {
         plgpu_column_release(out);
         return hip_fail(e, "rolling");
     }
     out->null_count = -1;
     return PLGPU_OK;
+}
+
+PLGPU_API int plgpu_rolling(const plgpu_column* values, int32_t kind, int64_t window_size, int64_t min_periods,
+                            int32_t center, plgpu_column* out, void* stream) {
+    return rolling_impl(values, nullptr, kind, window_size, min_periods, center, out, stream);
+}
+
+PLGPU_API int plgpu_rolling_segmented(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind,
+                                      int64_t window_size, int64_t min_periods, int32_t center, plgpu_column* out,
+                                      void* stream) {
+    if (seg_starts == nullptr) return fail(PLGPU_ERR_INVALID, "NULL argument");
+    return rolling_impl(values, seg_starts, kind, window_size, min_periods, center, out, stream);
 }

@@ -775,3 +775,130 @@ PLGPU_API int plgpu_arg_sort_multi(const plgpu_column* keys_in, int32_t nkeys, c
     if (rc) plgpu_column_release(out_idx);
     return rc;
 }
+
+// ------------------------------------------------ segment starts / inverse
+// plgpu_segment_starts: one streaming pass over 1..8 key columns.  Bit i of
+// the output is set when i == 0 or row i's key tuple differs from row
+// i - 1's (the group-by's equality: sort_code folds -0.0 into 0.0 and every
+// NaN into one, a null equals a null only); *unsorted is raised when some
+// row's tuple is below its predecessor's in the order plgpu_arg_sort_multi
+// gives with every column ascending, nulls first.
+namespace plgpu {
+
+struct SegKeys {
+    DevCol c[8];
+    int32_t n;
+};
+
+__global__ __launch_bounds__(256) void seg_starts_kernel(SegKeys k, int64_t n, uint64_t* __restrict__ out,
+                                                         uint32_t* __restrict__ unsorted) {
+    const int64_t words = (n + 63) / 64;
+    bool down = false;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < words * 64;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        bool start = false;
+        if (r < n) {
+            start = r == 0;
+            for (int j = 0; j < k.n && !start; ++j) {
+                const bool va = dev_valid(k.c[j], r - 1), vb = dev_valid(k.c[j], r);
+                if (va != vb) {
+                    start = true;
+                    down |= va;  // a value before a null
+                } else if (va) {
+                    const uint64_t a = sort_code(k.c[j], r - 1, false), b = sort_code(k.c[j], r, false);
+                    if (a != b) {
+                        start = true;
+                        down |= a > b;
+                    }
+                }
+            }
+        }
+        const uint64_t m = __ballot(start);
+        if ((threadIdx.x & 63) == 0) out[r >> 6] = m;
+    }
+    if (__ballot(down) != 0 && (threadIdx.x & 63) == 0) atomicOr(unsorted, 1u);
+}
+
+// out[idx[j]] = j
+__global__ __launch_bounds__(256) void invert_perm_kernel(const uint32_t* __restrict__ idx, int64_t n,
+                                                          uint32_t* __restrict__ out) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t t = idx[j];
+        if (t < n) out[t] = (uint32_t)j;  // (an index outside 0..n-1 is not a permutation's: never stored)
+    }
+}
+
+}  // namespace plgpu
+
+PLGPU_API int plgpu_segment_starts(const plgpu_column* keys, int32_t nkeys, plgpu_column* out_starts,
+                                   int32_t* out_sorted, void* stream) {
+    hipStream_t s = as_stream(stream);
+    if (keys == nullptr || out_starts == nullptr || out_sorted == nullptr)
+        return fail(PLGPU_ERR_INVALID, "NULL argument");
+    std::memset(out_starts, 0, sizeof *out_starts);
+    *out_sorted = 0;
+    if (nkeys < 1 || nkeys > 8) return fail(PLGPU_ERR_INVALID, "number of key columns must be 1..8");
+    const int64_t n = keys[0].length;
+    SegKeys k;
+    std::memset(&k, 0, sizeof k);
+    k.n = nkeys;
+    for (int j = 0; j < nkeys; ++j) {
+        const int32_t dt = keys[j].dtype;
+        if (!dtype_is_int(dt) && !dtype_is_float(dt) && dt != PLGPU_BOOL)
+            return fail(PLGPU_ERR_SCHEMA, "segment keys must be integer, float or Boolean columns");
+        if (keys[j].length != n) return fail(PLGPU_ERR_SHAPE, "key columns must have equal lengths");
+        k.c[j] = dev_col(keys[j]);
+    }
+    int rc = make_owned_column(out_starts, PLGPU_BOOL, n, false, s);
+    if (rc) return rc;
+    if (n == 0) {
+        *out_sorted = 1;
+        return PLGPU_OK;
+    }
+    uint32_t* flag = nullptr;
+    rc = dev_alloc((void**)&flag, 4, s);
+    uint32_t h = 1;
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemsetAsync(flag, 0, 4, s);
+        if (e == hipSuccess) {
+            KtScope kt("seg_starts_kernel", s);
+            seg_starts_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 256 * 64), 256, 0, s>>>(
+                k, n, (uint64_t*)out_starts->values, flag);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = hip_fail(e, "segment starts");
+    }
+    dev_free(flag, s);
+    if (rc) {
+        plgpu_column_release(out_starts);
+        return rc;
+    }
+    *out_sorted = h == 0 ? 1 : 0;
+    return PLGPU_OK;
+}
+
+PLGPU_API int plgpu_invert_permutation(const plgpu_column* idx, plgpu_column* out_idx, void* stream) {
+    hipStream_t s = as_stream(stream);
+    if (idx == nullptr || out_idx == nullptr) return fail(PLGPU_ERR_INVALID, "NULL argument");
+    std::memset(out_idx, 0, sizeof *out_idx);
+    if (idx->dtype != PLGPU_U32) return fail(PLGPU_ERR_SCHEMA, "a permutation is a UInt32 index column");
+    if (idx->validity != nullptr) return fail(PLGPU_ERR_SCHEMA, "a permutation has no null index");
+    const int64_t n = idx->length;
+    int rc = make_owned_column(out_idx, PLGPU_U32, n, false, s);
+    if (rc || n == 0) return rc;
+    {
+        KtScope kt("invert_perm_kernel", s);
+        invert_perm_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 256 * 64), 256, 0, s>>>(
+            (const uint32_t*)idx->values + idx->offset, n, (uint32_t*)out_idx->values);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        plgpu_column_release(out_idx);
+        return hip_fail(e, "invert permutation");
+    }
+    return PLGPU_OK;
+}

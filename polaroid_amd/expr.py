@@ -23,7 +23,7 @@ class Expr:
 
     def __init__(self, kind: str, args: Sequence["Expr"] = (), op: str | None = None,
                  value: Any = None, name: str | None = None):
-        self.kind = kind          # col | lit | bin | un | agg | alias | len
+        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | over | ...
         self.args = tuple(args)
         self.op = op
         self.value = value
@@ -51,6 +51,10 @@ class Expr:
             for n in a.meta_root_names():
                 if n not in out:
                     out.append(n)
+        if self.kind == "over":  # the function's columns, then the partition keys
+            for n in self.value:
+                if n not in out:
+                    out.append(n)
         return out
 
     def __repr__(self) -> str:
@@ -66,6 +70,9 @@ class Expr:
             return "len()"
         if self.kind == "rolling":
             return f"{self.args[0]!r}.rolling_{self.op}{self.value}"
+        if self.kind == "over":
+            keys = ", ".join(f'col("{k}")' for k in self.value)
+            return f"{self.args[0]!r}.over([{keys}])"
         if self.kind == "ternary":
             return f"when({self.args[0]!r}).then({self.args[1]!r}).otherwise({self.args[2]!r})"
         if self.kind == "cast":
@@ -190,16 +197,23 @@ class Expr:
         return Expr("alias", (self,), value=name)
 
     # ----------------------------------------------------- aggregations
-    def sum(self): return Expr("agg", (self,), op="sum")
-    def mean(self): return Expr("agg", (self,), op="mean")
-    def min(self): return Expr("agg", (self,), op="min")
-    def max(self): return Expr("agg", (self,), op="max")
-    def count(self): return Expr("agg", (self,), op="count")
-    def len(self): return Expr("agg", (self,), op="len")
-    def std(self, ddof: int = 1): return Expr("agg", (self,), op="std", value=int(ddof))
-    def var(self, ddof: int = 1): return Expr("agg", (self,), op="var", value=int(ddof))
-    def first(self): return Expr("agg", (self,), op="first")
-    def last(self): return Expr("agg", (self,), op="last")
+    def _agg(self, op: str, value: Any = None) -> "Expr":
+        if _has_over(self):
+            raise N.InvalidOperationError(
+                f"{self!r}.{op}(): a window expression (over) inside an aggregation's input is not supported "
+                "on the GPU executor")
+        return Expr("agg", (self,), op=op, value=value)
+
+    def sum(self): return self._agg("sum")
+    def mean(self): return self._agg("mean")
+    def min(self): return self._agg("min")
+    def max(self): return self._agg("max")
+    def count(self): return self._agg("count")
+    def len(self): return self._agg("len")
+    def std(self, ddof: int = 1): return self._agg("std", int(ddof))
+    def var(self, ddof: int = 1): return self._agg("var", int(ddof))
+    def first(self): return self._agg("first")
+    def last(self): return self._agg("last")
 
     # ------------------------------------------------- window / ordering
     def rolling_sum(self, window_size: int, weights=None, *, min_samples: int | None = None,
@@ -232,6 +246,55 @@ class Expr:
         """Fixed-window standard deviation (Expr.rolling_std)."""
         return _rolling(self, "std", window_size, weights, min_samples, center, ddof)
 
+    def over(self, partition_by: Any, *more_exprs: Any, order_by: Any = None,
+             mapping_strategy: str = "group_to_rows") -> "Expr":
+        """Expr.over: evaluate this expression on every group of the partition
+        keys, each result back at its row (polars-expr/src/expressions/
+        window.rs:356 WindowExpr::evaluate with WindowMapping::GroupsToRows).
+        Takes `<elementwise>.rolling_*(...)` and the aggregations sum / mean /
+        min / max / count / len / first / last / std / var of an elementwise
+        expression (or pl.len()), over plain key columns."""
+        keys: list[str] = []
+        items = [partition_by, *more_exprs]
+        while items:
+            it = items.pop(0)
+            if isinstance(it, (list, tuple)):
+                items = list(it) + items
+            elif isinstance(it, str):
+                keys.append(it)
+            elif isinstance(it, Expr) and it.kind == "col":
+                keys.append(it.value)
+            elif isinstance(it, Expr):
+                raise N.InvalidOperationError(
+                    f"over({it!r}): computed partition keys are not supported on the GPU executor "
+                    "(partition by plain columns)")
+            else:
+                raise N.InvalidOperationError(f"cannot interpret {it!r} as a partition key")
+        if not keys or builtins.len(keys) > N.MAX_KEYS:
+            raise N.InvalidOperationError("over() partitions by 1..8 plain key columns")
+        if builtins.len(set(keys)) != builtins.len(keys):
+            raise N.DuplicateError("over(): partition keys must be distinct columns")
+        if order_by is not None:
+            raise N.InvalidOperationError("over(order_by=...) is not supported on the GPU executor")
+        if mapping_strategy != "group_to_rows":
+            raise N.InvalidOperationError(
+                f"over(mapping_strategy={mapping_strategy!r}) is not supported on the GPU executor "
+                "(only 'group_to_rows')")
+        f = self
+        while f.kind == "alias":
+            f = f.args[0]
+        if f.kind == "rolling":
+            ok = _is_elementwise(f.args[0])
+        elif f.kind == "agg":
+            ok = f.op in _OVER_AGGS and _is_elementwise(f.args[0])
+        else:
+            ok = f.kind == "len"
+        if not ok:
+            raise N.InvalidOperationError(
+                f"{self!r}.over(...): the GPU executor evaluates over groups only rolling_* functions and the "
+                f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression")
+        return Expr("over", (self,), op="over", value=tuple(keys))
+
     def sort(self, *, descending: bool = False, nulls_last: bool = False) -> "Expr":
         return Expr("sort", (self,), op="sort", value=(bool(descending), bool(nulls_last)))
 
@@ -250,6 +313,21 @@ def _rolling(e: Expr, kind: str, window_size: int, weights, min_samples, center,
     if not 0 <= int(ddof) <= 255:
         raise N.InvalidOperationError("`ddof` must be in 0..255")
     return Expr("rolling", (e,), op=kind, value=(window_size, ms, bool(center), int(ddof)))
+
+
+_OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")
+_ELEMENTWISE = ("col", "lit", "bin", "un", "alias", "ternary", "cast", "fill_null", "strfn", "over")
+
+
+def _has_over(e: Expr) -> bool:
+    return e.kind == "over" or builtins.any(_has_over(a) for a in e.args)
+
+
+def _is_elementwise(e: Expr) -> bool:
+    """Row-by-row expressions (an over node counts: it yields one value per row)."""
+    if e.kind == "over":
+        return True
+    return e.kind in _ELEMENTWISE and builtins.all(_is_elementwise(a) for a in e.args)
 
 
 def _to_expr(v: Any) -> Expr:

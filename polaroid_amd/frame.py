@@ -16,7 +16,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _native as N
-from .expr import Expr, col, lit, lower, to_instr_array
+from .expr import Expr, _has_over, col, lit, lower, to_instr_array
 
 
 # ------------------------------------------------------------------ dtypes
@@ -540,7 +540,7 @@ class Series:
                      DataFrame([self])).alias(self.name)._with_logical(None)
 
     def _rolling(self, kind: int, window_size: int, min_samples: int | None, center: bool,
-                 ddof: int = 0) -> "Series":
+                 ddof: int = 0, seg: "Series | None" = None) -> "Series":
         """Fixed windows over Int32 / Int64 / Float64 on the device; the other
         dtypes the way polars-time's rolling dispatch takes them
         (rolling_window/dispatch.rs:228): rolling_sum of Int8 / Int16 / UInt8 /
@@ -548,7 +548,19 @@ class Series:
         Float64 and is rounded back; min / max keep the dtype.  var / std
         (dispatch.rs:478,526) run on the values as floats (`to_float`:
         integers as Float64; Float32 stays Float32, the variance rounded to
-        Float32 before std's square root, as the reference's f32 sqrt)."""
+        Float32 before std's square root, as the reference's f32 sqrt).
+        `seg` (a Boolean column of segment starts, Expr.over): every window
+        is also clipped to its row's segment (plgpu_rolling_segmented)."""
+        def run(src: "Series", code: int, ms: int) -> N.Column:
+            out = N.Column()
+            if seg is None:
+                N.check(N.lib().plgpu_rolling(C.byref(src._col), code, int(window_size), int(ms), int(center),
+                                              C.byref(out), None))
+            else:
+                N.check(N.lib().plgpu_rolling_segmented(C.byref(src._col), C.byref(seg._col), code,
+                                                        int(window_size), int(ms), int(center), C.byref(out), None))
+            return out
+
         lg = self._logical_dtype()
         is_var = kind in (N.ROLLING["var"], N.ROLLING["std"])
         if is_var:
@@ -560,12 +572,9 @@ class Series:
             src, f32 = self, phys is Float32
             if phys in (Int8, Int16, UInt8, UInt16, UInt32, UInt64, Float32):
                 src = self._cast_to(Float64)
-            out = N.Column()
             ms = window_size if min_samples is None else min_samples
             code = kind | (int(ddof) << 8) | ((1 << 16) if f32 and kind == N.ROLLING["std"] else 0)
-            N.check(N.lib().plgpu_rolling(C.byref(src._col), code, int(window_size), int(ms), int(center),
-                                          C.byref(out), None))
-            res = Series._from_native(self.name, out)
+            res = Series._from_native(self.name, run(src, code, ms))
             return res._cast_to(Float32) if f32 else res
         is_sum_mean = kind in (N.ROLLING["sum"], N.ROLLING["mean"])
         if lg is not None and is_sum_mean and not (kind == N.ROLLING["sum"] and isinstance(lg, Duration)):
@@ -581,11 +590,8 @@ class Series:
             src, back = self._cast_to(Float64), Float32
         elif phys is UInt64:
             raise N.InvalidOperationError("rolling windows over UInt64 are not supported on the GPU executor")
-        out = N.Column()
         ms = window_size if min_samples is None else min_samples
-        N.check(N.lib().plgpu_rolling(C.byref(src._col), kind, int(window_size), int(ms), int(center),
-                                      C.byref(out), None))
-        res = Series._from_native(self.name, out)
+        res = Series._from_native(self.name, run(src, kind, ms))
         if back is not None:
             res = res._cast_to(back)
         return res._with_logical(lg if not is_sum_mean or isinstance(lg, Duration) else None)
@@ -933,7 +939,12 @@ class LazyFrame:
         self._node = node
 
     def filter(self, *predicates: Expr, **constraints: Any) -> "LazyFrame":
-        return LazyFrame(("filter", self._node, _combine_predicates(predicates, constraints)))
+        pred = _combine_predicates(predicates, constraints)
+        if _has_over(pred):
+            raise N.InvalidOperationError(
+                "a window expression (over) in a filter predicate is not supported on the GPU executor: "
+                "compute it with with_columns first and filter on that column")
+        return LazyFrame(("filter", self._node, pred))
 
     def group_by(self, *by: Any, maintain_order: bool = False) -> "LazyGroupBy":
         return LazyGroupBy(self, by, maintain_order)
@@ -1331,7 +1342,142 @@ def _col_array(series: Sequence[Series]):
     return arr
 
 
-def _eval(expr: Expr, df: DataFrame) -> Series:
+# ------------------------------------------- window expressions over groups
+def _segment_starts(keys: Sequence[Series]) -> tuple[Series, bool]:
+    """(Boolean column: row i starts a run of equal key tuples, keys already
+    in the multi-key sort's ascending, nulls-first order)."""
+    out, srt = N.Column(), C.c_int32(0)
+    N.check(N.lib().plgpu_segment_starts(_col_array(keys), builtins.len(keys), C.byref(out), C.byref(srt), None))
+    return Series._from_native("__seg", out), bool(srt.value)
+
+
+def _over_sort_keys(df: DataFrame, names: Sequence[str]) -> list[Series]:
+    """The partition keys as columns plgpu_segment_starts and the multi-key
+    sort both take: a Categorical as its UInt32 codes, a String as the
+    group-by's short-string codes (at most 7 bytes each), logical types as
+    their physical integers."""
+    out = []
+    for nm in names:
+        if nm not in df._cols:
+            raise N.ComputeError(f'unable to find column "{nm}"; valid columns: {df.columns}')
+        s = df._cols[nm]
+        cc = s._cat_codes()
+        if cc is not None:
+            s = cc[1]
+        elif s.dtype is String:
+            codes, short = N.Column(), C.c_int32(0)
+            N.check(N.lib().plgpu_str_encode_short(C.byref(s._col), C.byref(codes), C.byref(short), None))
+            enc = Series._from_native(nm, codes)
+            if not short.value:
+                raise N.InvalidOperationError(
+                    f'over("{nm}"): a rolling function over String keys longer than 7 bytes is not supported '
+                    "on the GPU executor")
+            s = enc
+        out.append(s)
+    return out
+
+
+def _over_segments(keys: Sequence[str], df: DataFrame, cache: dict | None) -> tuple:
+    """(segment starts, sort permutation, its inverse) for rolling over
+    `keys`: the starts of the rows as they stand and no permutation when the
+    keys arrive sorted and option "over_presorted" is on, otherwise those of
+    the rows stably sorted by the keys.  `cache` (one select / with_columns
+    over one frame) shares them among the expressions with the same keys;
+    it holds two index columns until that select ends."""
+    ck = tuple(keys)
+    if cache is not None and ck in cache:
+        return cache[ck]
+    kcols = _over_sort_keys(df, keys)
+    starts, presorted = _segment_starts(kcols)
+    if presorted and N.get_option("over_presorted") != 0:
+        seg = (starts, None, None)
+    else:
+        k = builtins.len(kcols)
+        idx = N.Column()
+        zeros = (C.c_int32 * k)(*([0] * k))
+        N.check(N.lib().plgpu_arg_sort_multi(_col_array(kcols), k, zeros, zeros, C.byref(idx), None))
+        idx_s = Series._from_native("__idx", idx)
+        got = (N.Column * k)()
+        N.check(N.lib().plgpu_gather(_col_array(kcols), k, C.byref(idx_s._col), got, None))
+        starts, _ = _segment_starts([Series._from_native(kc.name, got[i]) for i, kc in enumerate(kcols)])
+        inv = N.Column()
+        N.check(N.lib().plgpu_invert_permutation(C.byref(idx_s._col), C.byref(inv), None))
+        seg = (starts, idx_s, Series._from_native("__inv", inv))
+    if cache is not None:
+        cache[ck] = seg
+    return seg
+
+
+def _over_rolling(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
+    """<elementwise>.rolling_*(...).over(keys): keys that arrive sorted need
+    one pass for the segment starts and the segmented kernel; otherwise a
+    stable sort by the keys, the same two steps on the gathered rows, and a
+    gather back through the inverse permutation (window.rs:524
+    MapStrategy::Map)."""
+    vals = _eval(f.args[0], df, cache)
+    w, ms, center, ddof = f.value
+    kind = N.ROLLING[f.op]
+    starts, idx_s, inv = _over_segments(keys, df, cache)
+    if starts.len() != vals.len():
+        raise N.ShapeError("over(): the partition keys and the values differ in length")
+    if idx_s is None:
+        return vals._rolling(kind, w, ms, center, ddof, seg=starts)
+    return vals.gather(idx_s)._rolling(kind, w, ms, center, ddof, seg=starts).gather(inv)
+
+
+def _over_agg(f: Expr, keys: Sequence[str], df: DataFrame) -> Series:
+    """<aggregation>.over(keys): group_by(keys, maintain_order=True).agg(f)
+    left-joined back on the keys with nulls_equal, in row order -- the
+    reference's own MapStrategy::Join (window.rs:548-628: hash_join_left of
+    the key columns with the group keys, nulls equal)."""
+    for nm in keys:
+        if nm not in df._cols:
+            raise N.ComputeError(f'unable to find column "{nm}"; valid columns: {df.columns}')
+    key = keys[0] if builtins.len(keys) == 1 else tuple(keys)
+    agg = f.alias("__over_agg")
+    df, _ = _cat_keys(df, key, [agg], None)  # Categorical keys as their codes on both sides of the join
+    g = _group_by(df, key, [agg], True, None, None)
+    left = DataFrame([df._cols[nm] for nm in keys])
+    out = _join(left, g, key, key, "_right", "m:m", True, "left", "left", None)
+    return out["__over_agg"]
+
+
+def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list) -> Expr:
+    """(A module-level function, not a closure of _lower_overs: a recursive
+    closure is a reference cycle that would keep `extra`, and with it every
+    materialised result column, alive until the cycle collector runs.)"""
+    if e.kind == "over":
+        f = e.args[0]
+        while f.kind == "alias":
+            f = f.args[0]
+        res = _over_rolling(f, e.value, df, cache) if f.kind == "rolling" else _over_agg(f, e.value, df)
+        name = f"__over{builtins.len(extra)}"
+        extra.append(res.alias(name))
+        return col(name)
+    if not e.args:
+        return e
+    args = tuple(_over_walk(a, df, cache, extra) for a in e.args)
+    if builtins.all(x is y for x, y in zip(args, e.args)):
+        return e
+    return Expr(e.kind, args, op=e.op, value=e.value, name=e._name)
+
+
+def _lower_overs(expr: Expr, df: DataFrame, cache: dict | None = None) -> tuple[Expr, DataFrame]:
+    """Materialise every over(...) sub-expression as a temporary column (as
+    _lower_strings does for String comparisons) and replace it by that
+    column, so the rest of the expression evaluates as usual."""
+    extra: list[Series] = []
+    new = _over_walk(expr, df, cache, extra)
+    return new, DataFrame(list(df._cols.values()) + extra)
+
+
+def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
+    """`overs`: what the over() nodes of one select / with_columns share
+    (_over_segments), valid for this `df` alone."""
+    if _has_over(expr):
+        name = expr.output_name()
+        expr, df = _lower_overs(expr, df, overs)
+        return _eval(expr, df).alias(name)
     if expr.kind in ("col",) or (expr.kind == "alias" and expr.args[0].kind == "col"):
         return df._cols[expr.meta_root_names()[0]].alias(expr.output_name())
     base = expr.args[0] if expr.kind == "alias" else expr
@@ -1937,7 +2083,8 @@ def _execute(node: tuple, info: dict | None = None) -> DataFrame:
         if builtins.any(_agg_base(e).kind in ("agg", "len") for e in node[2]):
             raise N.InvalidOperationError("mixing aggregations and elementwise expressions in one select is not "
                                           "supported on the GPU executor")
-        new = [_eval(e, df) for e in node[2]]
+        overs: dict = {}
+        new = [_eval(e, df, overs) for e in node[2]]
         if kind == "select":
             return DataFrame(new)
         cols = dict(df._cols)

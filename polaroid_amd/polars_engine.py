@@ -107,6 +107,10 @@ class _Translator:
         # categorical.rs:58 uses_lexical_ordering; sort/categorical.rs:74):
         # the GPU handles them as strings, so ordered uses stay on polars
         self.enums: set[str] = set()
+        # the input schema of the Select / HStack being translated (dtype
+        # gates of a window's aggregation, as in a group-by); None wherever
+        # a Window node is not translated (Filter, an aggregation's input)
+        self._schema: dict | None = None
 
     # ---------------------------------------------------------- expressions
     def _is_enum(self, node: int) -> bool:
@@ -183,7 +187,41 @@ class _Translator:
                 except N.InvalidOperationError as exc:
                     raise Unsupported(str(exc)) from exc
             raise Unsupported(f"function {fname}")
+        if k == "Window":
+            return self.window(e)
         raise Unsupported(f"expression {k}")
+
+    def window(self, e) -> Expr:
+        """Window (expr_nodes.rs:400): an aggregation the group-by translator
+        takes, over plain partition columns, no order_by, mapped back to the
+        rows (WindowMapping::GroupsToRows) -> Expr.over.  Rolling functions
+        never arrive here: the visitor raises NotImplementedError for
+        FunctionExpr::RollingExpr (expr_nodes.rs:1192), which `view` turns
+        into Unsupported."""
+        if self._schema is None:
+            # the mirror lowers an over node in select / with_columns only
+            # (frame._lower_overs), never below an aggregation
+            raise Unsupported("window outside the expressions of a select / with_columns")
+        if e.order_by is not None:
+            raise Unsupported("window with order_by")
+        kind = str(getattr(e.options, "kind", e.options))
+        if kind != "groups_to_rows":
+            raise Unsupported(f"window mapping {kind}")
+        keys = []
+        for p in e.partition_by:
+            kx = self.view(p)
+            if _name(kx) != "Column":
+                raise Unsupported("window partitioned by an expression")
+            keys.append(str(kx.name))
+        if not 1 <= len(keys) <= 8:
+            raise Unsupported("window partitioned by more than 8 columns")
+        if _name(self.view(e.function)) not in ("Agg", "Len"):
+            raise Unsupported(f"window function {_name(self.view(e.function))}")
+        f = self.agg(e.function, None, self._schema)
+        try:
+            return f.over(keys)
+        except N.PolaroidError as exc:
+            raise Unsupported(str(exc)) from exc
 
     def input_schema(self, input_node: int) -> dict:
         """Output schema of plan node `input_node` (visit.rs get_schema at that
@@ -274,7 +312,13 @@ class _Translator:
             if name in ("min", "max") and str(arg.name) in self.enums:
                 raise Unsupported(f"{name} of an Enum column (category order)")
         else:
-            c = self.expr(e.arguments[0])  # raises Unsupported outside the elementwise path
+            # (no window below an aggregation: Expr refuses it, and polars
+            # keeps the query)
+            held, self._schema = self._schema, None
+            try:
+                c = self.expr(e.arguments[0])  # raises Unsupported outside the elementwise path
+            finally:
+                self._schema = held
         if name in ("sum", "mean"):
             return getattr(c, name)()
         if name in ("min", "max"):
@@ -363,9 +407,13 @@ class _Translator:
             if k in ("Select", "HStack"):
                 exprs = node.expr if k == "Select" else node.exprs
                 out = []
-                for ei in exprs:
-                    x = self.expr(ei.node)
-                    out.append(x if x.output_name() == ei.output_name else x.alias(ei.output_name))
+                self._schema = self.input_schema(node.input)
+                try:
+                    for ei in exprs:
+                        x = self.expr(ei.node)
+                        out.append(x if x.output_name() == ei.output_name else x.alias(ei.output_name))
+                finally:
+                    self._schema = None
                 return ("select" if k == "Select" else "with_columns", child, out)
             # GroupBy
             opts = node.options
