@@ -517,8 +517,8 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
         all8 = hipMemGetInfo(&fr, &tot) == hipSuccess && (uint64_t)ncols * (uint64_t)n * 8 <= fr / 4;
     }
     if (all8) {
-        uint64_t* status = nullptr;  // ntiles words + the ticket
-        if ((rc = dev_alloc((void**)&status, (ntiles + 1) * 8, s))) return rc;
+        DevBuf<uint64_t> status;  // ntiles words + the ticket
+        if ((rc = status.alloc((ntiles + 1) * 8, s))) return rc;
         Scatter8Args sa;
         std::memset(&sa, 0, sizeof sa);
         for (int i = 0; i < ncols && !rc; ++i) {
@@ -547,7 +547,6 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
             if (e != hipSuccess) rc = hip_fail(e, "filter_fused8_kernel");
             if (!rc && (last & ~kFtValue) != kFtIncl) rc = fail(PLGPU_ERR_CAPACITY, "internal: filter prefix not published");
         }
-        dev_free(status, s);
         if (rc) {
             for (int i = 0; i < ncols; ++i) plgpu_column_release(&out_cols[i]);
             return rc;
@@ -558,21 +557,15 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
         return PLGPU_OK;
     }
 
-    uint64_t* mask_words = nullptr;
-    uint32_t* counts = nullptr;
-    uint64_t* offs = nullptr;  // ntiles offsets + 1 total
-    uint64_t* scan_part = nullptr;
+    DevBuf<uint64_t> mask_words;
+    DevBuf<uint32_t> counts;
+    DevBuf<uint64_t> offs, scan_part;  // offs: ntiles offsets + 1 total
     uint64_t total = 0;
     if (ntiles > 0) {
-        if ((rc = dev_alloc((void**)&mask_words, ntiles * kTileWords * 8, s))) return rc;
-        if ((rc = dev_alloc((void**)&counts, ntiles * 4, s))) { dev_free(mask_words, s); return rc; }
-        if ((rc = dev_alloc((void**)&offs, (ntiles + 1) * 8, s)) ||
-            (rc = dev_alloc((void**)&scan_part, ((ntiles + kScanChunk - 1) / kScanChunk + 1) * 8, s))) {
-            dev_free(mask_words, s);
-            dev_free(counts, s);
-            dev_free(offs, s);
-            return rc;
-        }
+        if ((rc = mask_words.alloc(ntiles * kTileWords * 8, s))) return rc;
+        if ((rc = counts.alloc(ntiles * 4, s))) return rc;
+        if ((rc = offs.alloc((ntiles + 1) * 8, s))) return rc;
+        if ((rc = scan_part.alloc(((ntiles + kScanChunk - 1) / kScanChunk + 1) * 8, s))) return rc;
         const int g = grid_for(ntiles, 1, 256 * 8);
         {
             KtScope kt("filter_mask_kernel", s);
@@ -593,11 +586,11 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
         PLGPU_HIP(hipMemcpyAsync(&total, offs + ntiles, 8, hipMemcpyDeviceToHost, s));
         PLGPU_HIP(hipStreamSynchronize(s));
     }
-    int64_t* sel_rows = nullptr;  // selected row ids, for string columns
+    DevBuf<int64_t> sel_rows;  // selected row ids, for string columns
     for (int i = 0; i < ncols && !rc; ++i) {
         if (cols[i].dtype != PLGPU_STR) continue;
         if (sel_rows == nullptr) {
-            if ((rc = dev_alloc((void**)&sel_rows, std::max<uint64_t>(total, 1) * 8, s))) break;
+            if ((rc = sel_rows.alloc(std::max<uint64_t>(total, 1) * 8, s))) break;
             if (total > 0) {
                 DevCol rows;
                 std::memset(&rows, 0, sizeof rows);
@@ -667,11 +660,6 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
         PLGPU_HIP(hipGetLastError());
         if (!need_valid && cols[i].dtype == PLGPU_BOOL) out_cols[i].null_count = 0;
     }
-    dev_free(mask_words, s);
-    dev_free(counts, s);
-    dev_free(offs, s);
-    dev_free(scan_part, s);
-    dev_free(sel_rows, s);
     if (rc) {
         for (int i = 0; i < ncols; ++i) plgpu_column_release(&out_cols[i]);
         return rc;

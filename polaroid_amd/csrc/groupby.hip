@@ -1594,12 +1594,6 @@ static int plan_groupby(const plgpu_column* key, const plgpu_column* cols, int32
     return PLGPU_OK;
 }
 
-static int log2_ceil(int64_t x) {
-    int b = 0;
-    while ((int64_t(1) << b) < x) ++b;
-    return b;
-}
-
 // Size the LDS table / grid from the distinct-key sample of the plan kernel.
 static void size_tables(Plan* pl, uint64_t distinct, uint64_t sampled, int* gbits_out, int64_t hll_est = -1,
                         int64_t* est_out = nullptr) {
@@ -1806,9 +1800,9 @@ struct GbRun {
     DevProgram dp;
     int pred = 0;
     hipStream_t s = nullptr;
-    uint64_t* status = nullptr;  // ST_WORDS words + kMaxAcc int32 bottoms
-    int32_t* bottoms = nullptr;
-    uint64_t* gtab = nullptr;
+    DevBuf<uint64_t> status;     // ST_WORDS words + kMaxAcc int32 bottoms
+    int32_t* bottoms = nullptr;  // (inside status)
+    DevBuf<uint64_t> gtab;
     uint64_t st[ST_WORDS];
     int32_t hb[kMaxAcc];         // host copy of the fixed-point bottoms
     int gbits = 10;
@@ -1821,8 +1815,8 @@ struct GbRun {
     uint32_t wide = 0;                       // accs summed by the wide fallback
     int wide_exmin[kMaxAcc] = {0};
     int wide_exmax[kMaxAcc] = {0};
-    int64_t* wide_digits[kMaxAcc] = {nullptr};
-    double* wide_sum[kMaxAcc] = {nullptr};
+    DevBuf<int64_t> wide_digits[kMaxAcc];
+    DevBuf<double> wide_sum[kMaxAcc];
     int64_t est_groups = -1;                 // plan's group estimate (sampled / HLL)
     bool wide_round = true;                  // gb_wide rounds (false: multi-GPU partial digits)
     std::string plan_ckey;                   // plan-cache key when the statistics came from the cache
@@ -1842,12 +1836,12 @@ struct GbRun {
     // read only through gb_finalize), on for this attempt (compact_now)
     bool compact_ok = false;
     bool compact_now = false;
-    uint32_t* region_cnt = nullptr;
-    uint64_t* rtab = nullptr;                // compact regions' table (GbParams::rtab)
+    DevBuf<uint32_t> region_cnt;
+    DevBuf<uint64_t> rtab;                   // compact regions' table (GbParams::rtab)
     bool has_null_key = false;               // partitioned: null keys written as null_key (GbParams)
     int64_t null_key = 0;
-    uint64_t* pbuf = nullptr;
-    uint64_t* prange = nullptr;              // scan of the count matrix + partition bounds
+    DevBuf<uint64_t> pbuf;
+    DevBuf<uint64_t> prange;                 // scan of the count matrix + partition bounds
     const uint64_t* part_range = nullptr;    // P + 1 partition boundaries (inside prange)
     int64_t part_rows_total = 0;
     std::vector<uint64_t> part_hrange;       // host copy of the P + 1 bounds
@@ -1867,16 +1861,6 @@ struct GbRun {
         std::memset(&pout, 0, sizeof pout);
     }
     ~GbRun() {
-        for (int a = 0; a < kMaxAcc; ++a) {
-            dev_free(wide_digits[a], s);
-            dev_free(wide_sum[a], s);
-        }
-        dev_free(gtab, s);
-        dev_free(status, s);
-        dev_free(pbuf, s);
-        dev_free(region_cnt, s);
-        dev_free(rtab, s);
-        dev_free(prange, s);
         for (auto& c : mat) plgpu_column_release(&c);
     }
 };
@@ -2001,7 +1985,7 @@ static int gb_prepare(GbRun& R, const plgpu_column* key, const plgpu_column* col
     // global distinct-key set; one allocation, one memset
     static_assert(ST_WORDS * 8 + kMaxAcc * 4 <= kPlanSetWord * 8, "status layout");
     const size_t bytes = (size_t)(kPlanSetWord + kPlanSetSlots) * 8;
-    if ((rc = dev_alloc((void**)&R.status, bytes, R.s))) return rc;
+    if ((rc = R.status.alloc(bytes, R.s))) return rc;
     R.bottoms = (int32_t*)(R.status + ST_WORDS);
     R.pl.p.status = R.status;
     R.pl.p.bottoms = R.bottoms;
@@ -2179,9 +2163,9 @@ void gb_plan_cache_clear() {
 
 // Distinct keys of the key column by HyperLogLog (gb_hll_kernel, ~1.6 %).
 static int gb_hll_count(GbRun& R, int64_t* out) {
-    uint32_t* regs = nullptr;
+    DevBuf<uint32_t> regs;
     std::vector<uint32_t> h(1 << kHllBits);
-    int rc = dev_alloc((void**)&regs, h.size() * 4, R.s);
+    int rc = regs.alloc(h.size() * 4, R.s);
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(regs, 0, h.size() * 4, R.s);
     if (e == hipSuccess) {
@@ -2191,7 +2175,6 @@ static int gb_hll_count(GbRun& R, int64_t* out) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), regs, h.size() * 4, hipMemcpyDeviceToHost, R.s);
     if (e == hipSuccess) e = hipStreamSynchronize(R.s);
-    dev_free(regs, R.s);
     if (e != hipSuccess) return hip_fail(e, "gb_hll_kernel");
     *out = (int64_t)hll_estimate(h.data());
     return PLGPU_OK;
@@ -2518,7 +2501,7 @@ static hipError_t gbp_pass1(const GbRun& R, bool f8, bool nul, const PsGeom& g, 
 
 // Partition buffers for `rows` selected rows: key, nacc columns, row ids,
 // null bits (nul).
-static int gbp_alloc(GbRun& R, int64_t sel, bool nul, uint64_t** buf, PartOut* o) {
+static int gbp_alloc(GbRun& R, int64_t sel, bool nul, DevBuf<uint64_t>* owner, PartOut* o) {
     const GbParams& p = R.pl.p;
     // a multiple of 16 rows, so every column's buffer starts on a 128-B line
     // (pair loads; the level-2 tiles' aligned block loads)
@@ -2526,13 +2509,14 @@ static int gbp_alloc(GbRun& R, int64_t sel, bool nul, uint64_t** buf, PartOut* o
     const bool want_rows = p.f_first >= 0 || p.f_last >= 0;
     const size_t rwords = want_rows ? ((size_t)rows + 1) / 2 : 0;
     const size_t words = (size_t)rows * (1 + p.nacc) + rwords + (nul ? ((size_t)rows + 7) / 8 : 0);
-    int rc = dev_alloc((void**)buf, words * 8, R.s);
+    int rc = owner->alloc(words * 8, R.s);
     if (rc) return rc;
+    uint64_t* buf = owner->get();
     std::memset(o, 0, sizeof *o);
-    o->key = *buf;
-    for (int a = 0; a < p.nacc; ++a) o->acc[a] = *buf + (size_t)rows * (1 + a);
-    o->rows = want_rows ? (uint32_t*)(*buf + (size_t)rows * (1 + p.nacc)) : nullptr;
-    o->nulls = nul ? (uint8_t*)(*buf + (size_t)rows * (1 + p.nacc) + rwords) : nullptr;
+    o->key = buf;
+    for (int a = 0; a < p.nacc; ++a) o->acc[a] = buf + (size_t)rows * (1 + a);
+    o->rows = want_rows ? (uint32_t*)(buf + (size_t)rows * (1 + p.nacc)) : nullptr;
+    o->nulls = nul ? (uint8_t*)(buf + (size_t)rows * (1 + p.nacc) + rwords) : nullptr;
     o->cap = rows;
     return PLGPU_OK;
 }
@@ -2580,17 +2564,16 @@ static int gb_partition(GbRun& R) {
     g1.sh = b1 ? 64 - b1 : 0;
     g1.dbits = b1;
     const int64_t ncnt1 = g1.ntiles << b1;
-    uint32_t* cnt = nullptr;
-    uint64_t* part = nullptr;
+    DevBuf<uint32_t> cnt;
+    DevBuf<uint64_t> part;
     // final bounds (P + 1), then the level-1 bounds (P1 + 1) of a two-pass run
-    int rc = dev_alloc((void**)&R.prange, (size_t)(P + 1 + (two ? P1 + 1 : 0)) * 8, s);
+    int rc = R.prange.alloc((size_t)(P + 1 + (two ? P1 + 1 : 0)) * 8, s);
     uint64_t* range = R.prange;
     uint64_t* range1 = two ? R.prange + P + 1 : range;
-    if (!rc) rc = dev_alloc((void**)&cnt, (size_t)ncnt1 * 4, s);
+    if (!rc) rc = cnt.alloc((size_t)ncnt1 * 4, s);
     // (+ the key range slots of a sentinel run)
     if (!rc)
-        rc = dev_alloc((void**)&part, (size_t)((ncnt1 + kScanChunk - 1) / kScanChunk + 2 + 2 * kKeyRangeSlots) * 8,
-                       s);
+        rc = part.alloc((size_t)((ncnt1 + kScanChunk - 1) / kScanChunk + 2 + 2 * kKeyRangeSlots) * 8, s);
     std::vector<uint64_t> hr1((size_t)P1 + 1);
     std::vector<int64_t> krange(2 * kKeyRangeSlots);
     for (int i = 0; i < kKeyRangeSlots; ++i) krange[2 * i] = INT64_MAX, krange[2 * i + 1] = INT64_MIN;
@@ -2628,24 +2611,19 @@ static int gb_partition(GbRun& R) {
             nul_out = false;
         }
     }
-    uint64_t* buf1 = nullptr;
+    DevBuf<uint64_t> buf1;
     PartOut out1;
     if (!rc) rc = gbp_alloc(R, (int64_t)hr1[P1], nul_out, &buf1, &out1);
     if (!rc) {
         const hipError_t e = gbp_pass1(R, f8, nul, g1, cnt, part, true, out1);
         if (e != hipSuccess) rc = hip_fail(e, "gbp_scatter_kernel");
     }
-    dev_free(cnt, s);
-    dev_free(part, s);
-    cnt = nullptr;
-    part = nullptr;
-    if (rc) {
-        dev_free(buf1, s);
-        return rc;
-    }
+    cnt.reset();  // (level 2 allocates its own)
+    part.reset();
+    if (rc) return rc;
     std::vector<uint64_t> hr;
     if (!two) {
-        R.pbuf = buf1;
+        R.pbuf = std::move(buf1);
         R.pout = out1;
         hr = hr1;
     } else {
@@ -2667,10 +2645,10 @@ static int gb_partition(GbRun& R) {
         g2.has_sentinel = g1.has_sentinel;
         g2.sentinel = g1.sentinel;
         const int64_t ncnt2 = g2.ntiles << b2;
-        uint32_t* meta = nullptr;
-        rc = dev_alloc((void**)&meta, (size_t)(P1 + 1 + std::max<int64_t>(g2.ntiles, 1)) * 4, s);
-        if (!rc) rc = dev_alloc((void**)&cnt, (size_t)std::max<int64_t>(ncnt2, 1) * 4, s);
-        if (!rc) rc = dev_alloc((void**)&part, (size_t)((ncnt2 + kScanChunk - 1) / kScanChunk + 2) * 8, s);
+        DevBuf<uint32_t> meta;
+        rc = meta.alloc((size_t)(P1 + 1 + std::max<int64_t>(g2.ntiles, 1)) * 4, s);
+        if (!rc) rc = cnt.alloc((size_t)std::max<int64_t>(ncnt2, 1) * 4, s);
+        if (!rc) rc = part.alloc((size_t)((ncnt2 + kScanChunk - 1) / kScanChunk + 2) * 8, s);
         hr.resize((size_t)P + 1);
         if (!rc) {
             g2.tstart = meta;
@@ -2698,10 +2676,6 @@ static int gb_partition(GbRun& R) {
                                          : gbp_pass<0, true, true>(R, g2, out1, cnt, part, true, R.pout);
             if (e != hipSuccess) rc = hip_fail(e, "gbp_scatter_kernel (level 2)");
         }
-        dev_free(cnt, s);
-        dev_free(part, s);
-        dev_free(meta, s);
-        dev_free(buf1, s);
         if (rc) return rc;
     }
     uint64_t maxpart = 0;
@@ -2753,15 +2727,13 @@ int radix_partition8(const DevCol& key, const DevCol* cols, int ncols, int64_t n
     R.pbits = bits;
     const int rc = gb_partition(R);
     if (rc) return rc;
-    out->buf = R.pbuf;
+    out->buf = std::move(R.pbuf);
     out->key = R.pout.key;
     for (int i = 0; i < ncols; ++i) out->col[i] = R.pout.acc[i];
-    out->range = R.prange;
+    out->range = std::move(R.prange);
     out->bounds = R.part_range;
     out->hrange = R.part_hrange;
     out->levels = R.part_levels;
-    R.pbuf = nullptr;  // owned by the caller now
-    R.prange = nullptr;
     return PLGPU_OK;
 }
 
@@ -2821,10 +2793,8 @@ static hipError_t launch_partitioned(const GbRun& R) {
 
 static int gb_alloc_table(GbRun& R) {
     GbParams& p = R.pl.p;
-    dev_free(R.gtab, R.s);
-    dev_free(R.rtab, R.s);
-    R.gtab = nullptr;
-    R.rtab = nullptr;
+    R.gtab.reset();  // (before the new tables are allocated)
+    R.rtab.reset();
     p.rtab = nullptr;
     p.rcap = 0;
     p.region_cnt = nullptr;
@@ -2835,7 +2805,7 @@ static int gb_alloc_table(GbRun& R) {
         // whole where read, never initialised) and a small hashed overflow
         // table (plain probing) for the keys that find no LDS slot
         p.rcap = int64_t(1) << (R.pbits + R.part_lbits);
-        int rc = dev_alloc((void**)&R.rtab, (size_t)p.rcap * p.nfields * 8, R.s);
+        int rc = R.rtab.alloc((size_t)p.rcap * p.nfields * 8, R.s);
         if (rc) return rc;
         p.rtab = R.rtab;
         p.region_cnt = R.region_cnt;
@@ -2844,7 +2814,7 @@ static int gb_alloc_table(GbRun& R) {
     }
     p.gcap = int64_t(1) << p.gbits;
     const size_t wpf = (size_t)(p.gcap + 2);
-    int rc = dev_alloc((void**)&R.gtab, wpf * p.nfields * 8, R.s);
+    int rc = R.gtab.alloc(wpf * p.nfields * 8, R.s);
     if (rc) return rc;
     p.gtab = R.gtab;
     const int ig = (int)std::min<int64_t>((int64_t)(wpf + 255) / 256, 256 * 8);
@@ -2894,15 +2864,13 @@ static int gb_wide(GbRun& R, bool round = true) {
     GbParams& p = R.pl.p;
     for (int a = 0; a < p.nacc; ++a) {
         if (!((R.wide >> a) & 1u)) continue;
-        dev_free(R.wide_digits[a], R.s);
-        dev_free(R.wide_sum[a], R.s);
-        R.wide_digits[a] = nullptr;
-        R.wide_sum[a] = nullptr;
+        R.wide_digits[a].reset();
+        R.wide_sum[a].reset();
         const int exmin = R.wide_exmin[a];
         const int nwords = wide_nwords(exmin, R.wide_exmax[a]);
         const size_t slots = (size_t)(p.gcap + 2);
-        int rc = dev_alloc((void**)&R.wide_digits[a], slots * nwords * 8, R.s);
-        if (!rc && round) rc = dev_alloc((void**)&R.wide_sum[a], slots * 8, R.s);
+        int rc = R.wide_digits[a].alloc(slots * nwords * 8, R.s);
+        if (!rc && round) rc = R.wide_sum[a].alloc(slots * 8, R.s);
         if (rc) return rc;
         PLGPU_HIP(hipMemsetAsync(R.wide_digits[a], 0, slots * nwords * 8, R.s));
         const int g = std::max(1, num_cus() * 8);
@@ -2955,7 +2923,7 @@ static int gb_main(GbRun& R, bool auto_refit, bool* refit, int32_t* hint) {
         R.compact_now = R.compact_ok && R.part && n > 0 && pl.sum_only && pl.limbs == 2 && R.rbits > 0 &&
                         R.part_blocks == 1 && R.wide == 0 && options().part_compact != 0;
         if (R.compact_now && R.region_cnt == nullptr &&
-            (rc = dev_alloc((void**)&R.region_cnt, ((size_t)1 << R.pbits) * 4, R.s)))
+            (rc = R.region_cnt.alloc(((size_t)1 << R.pbits) * 4, R.s)))
             break;
         if ((rc = gb_alloc_table(R))) break;
         PLGPU_HIP(hipMemcpyAsync(R.bottoms, R.hb, sizeof R.hb, hipMemcpyHostToDevice, R.s));
@@ -3102,9 +3070,9 @@ static void gb_fill_info(const GbRun& R, plgpu_groupby_info* info) {
 
 // Global table -> output columns (+ first-occurrence order, key narrowing).
 // `keep_first` (R.want_first): receives each output group's first selected
-// row, in output order (device buffer, caller frees).
+// row, in output order (device buffer).
 static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_column* out_aggs,
-                       uint64_t** keep_first = nullptr) {
+                       DevBuf<uint64_t>* keep_first = nullptr) {
     Plan& pl = R.pl;
     GbParams& p = pl.p;
     hipStream_t s = R.s;
@@ -3127,8 +3095,8 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
         }
         if (rc == PLGPU_OK) rc = make_owned_column(&out_aggs[i], o.out_dtype, groups, nullable, s);
     }
-    uint64_t* first = nullptr;
-    if (rc == PLGPU_OK && (R.maintain || keep_first) && groups > 0) rc = dev_alloc((void**)&first, groups * 8, s);
+    DevBuf<uint64_t> first;
+    if (rc == PLGPU_OK && (R.maintain || keep_first) && groups > 0) rc = first.alloc(groups * 8, s);
     if (rc == PLGPU_OK && groups > 0) {
         fp.nout = naggs;
         for (int i = 0; i < naggs; ++i) {
@@ -3141,27 +3109,23 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
         fp.out_first = first;
         fp.cap = groups;
         for (int a = 0; a < kMaxAcc; ++a) fp.wide[a] = R.wide_sum[a];
-        uint8_t* vbytes = nullptr;
-        rc = dev_alloc((void**)&vbytes, (size_t)(1 + naggs) * groups, s);
+        DevBuf<uint8_t> vbytes;
+        rc = vbytes.alloc((size_t)(1 + naggs) * groups, s);
         if (rc) {
-            dev_free(first, s);
             plgpu_column_release(out_key);
             for (int i = 0; i < naggs; ++i) plgpu_column_release(&out_aggs[i]);
             return rc;
         }
         fp.vbytes = vbytes;
         const int fg = (int)std::min<int64_t>((p.gcap + 2 + 255) / 256, 256 * 16);
-        uint64_t* roff = nullptr;  // compact regions: scan of the region counts + scratch
+        DevBuf<uint64_t> roff;  // compact regions: scan of the region counts + scratch
         const int nreg = R.compact_now ? 1 << R.pbits : 0;
         if (nreg) {
             const int64_t nb = std::max<int64_t>(1, (nreg + kScanChunk - 1) / kScanChunk);
-            rc = dev_alloc((void**)&roff, (size_t)(nreg + 1 + nb + 2) * 8, s);
+            rc = roff.alloc((size_t)(nreg + 1 + nb + 2) * 8, s);
             if (!rc && scan_exclusive<uint32_t>(R.region_cnt, nreg, roff, roff + nreg + 1, s) != hipSuccess)
                 rc = fail(PLGPU_ERR_HIP, "region count scan");
             if (rc) {
-                dev_free(roff, s);
-                dev_free(vbytes, s);
-                dev_free(first, s);
                 plgpu_column_release(out_key);
                 for (int i = 0; i < naggs; ++i) plgpu_column_release(&out_aggs[i]);
                 return rc;
@@ -3182,8 +3146,8 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
             gb_pack_valid_kernel<<<(unsigned)std::min<int64_t>((work + 255) / 256, 4096), 256, 0, s>>>(vbytes, groups,
                                                                                                        pv);
         }
-        dev_free(vbytes, s);
-        dev_free(roff, s);
+        vbytes.reset();
+        roff.reset();
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "gb_finalize_kernel");
         uint64_t produced = 0, var_out = 0;
@@ -3217,8 +3181,8 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
         fc.length = groups;
         fc.values = first;
         rc = plgpu_arg_sort(&fc, 0, 0, &pidx, s);
-        int64_t* dperm = nullptr;
-        if (rc == PLGPU_OK) rc = dev_alloc((void**)&dperm, groups * 8, s);
+        DevBuf<int64_t> dperm;
+        if (rc == PLGPU_OK) rc = dperm.alloc(groups * 8, s);
         if (rc == PLGPU_OK) {
             const int gg = (int)std::min<int64_t>((groups + 255) / 256, 4096);
             widen_u32_kernel<<<gg, 256, 0, s>>>((const uint32_t*)pidx.values, dperm, groups);
@@ -3260,18 +3224,17 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
             for (int i = 0; i < naggs && rc == PLGPU_OK; ++i) rc = permute(&out_aggs[i]);
             if (rc == PLGPU_OK && keep_first) {
                 // first rows in output order
-                uint64_t* sf = nullptr;
-                rc = dev_alloc((void**)&sf, groups * 8, s);
+                DevBuf<uint64_t> sf;
+                rc = sf.alloc(groups * 8, s);
                 if (rc == PLGPU_OK) {
                     gather_kernel<uint64_t><<<gg, 256, 0, s>>>(first, dperm, sf, groups);
-                    dev_free(first, s);
-                    first = sf;
+                    first = std::move(sf);
                 }
             }
             hipError_t e = hipGetLastError();
             if (rc == PLGPU_OK && e != hipSuccess) rc = hip_fail(e, "permute");
         }
-        dev_free(dperm, s);
+        dperm.reset();
         plgpu_column_release(&pidx);
     }
     if (rc == PLGPU_OK && R.key_dtype != PLGPU_I64 && dtype_bytes(R.key_dtype) > 0) {
@@ -3295,11 +3258,7 @@ static int gb_finalize(GbRun& R, int32_t naggs, plgpu_column* out_key, plgpu_col
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "finalize sync");
     }
-    if (rc == PLGPU_OK && keep_first) {
-        *keep_first = first;
-        first = nullptr;
-    }
-    dev_free(first, s);
+    if (rc == PLGPU_OK && keep_first) *keep_first = std::move(first);
     if (rc) {
         plgpu_column_release(out_key);
         for (int i = 0; i < naggs; ++i) plgpu_column_release(&out_aggs[i]);
@@ -3595,8 +3554,8 @@ PLGPU_API int plgpu_gb_partial_export(plgpu_gb_partial* h, void* dst_records, in
     const int rw = wide_layout(R, wr);
     for (int i = 0; i < wr.n; ++i)
         if (wr.digits[i] == nullptr) return fail(PLGPU_ERR_INVALID, "wide: digits missing");
-    uint64_t* counts = nullptr;  // [W] counts, [W] cursors
-    int rc = dev_alloc((void**)&counts, (size_t)W * 16, s);
+    DevBuf<uint64_t> counts;  // [W] counts, [W] cursors
+    int rc = counts.alloc((size_t)W * 16, s);
     if (rc) return rc;
     PLGPU_HIP(hipMemsetAsync(counts, 0, (size_t)W * 16, s));
     const int fg = (int)std::min<int64_t>((p.gcap + 2 + 255) / 256, 256 * 16);
@@ -3611,16 +3570,12 @@ PLGPU_API int plgpu_gb_partial_export(plgpu_gb_partial* h, void* dst_records, in
         out_counts[w] = (int64_t)hc[w];
     }
     if (run > 0) {
-        if (dst_records == nullptr) {
-            dev_free(counts, s);
-            return fail(PLGPU_ERR_INVALID, "dst_records is NULL");
-        }
+        if (dst_records == nullptr) return fail(PLGPU_ERR_INVALID, "dst_records is NULL");
         PLGPU_HIP(hipMemcpyAsync(counts + W, cur.data(), (size_t)W * 8, hipMemcpyHostToDevice, s));
         gb_export_kernel<<<fg, 256, 0, s>>>(p, W, counts + W, (uint64_t*)dst_records, wr, rw);
         PLGPU_HIP(hipGetLastError());
     }
     PLGPU_HIP(hipStreamSynchronize(s));
-    dev_free(counts, s);
     return PLGPU_OK;
 }
 
@@ -3656,8 +3611,8 @@ PLGPU_API int plgpu_gb_route(const plgpu_column* key, int32_t world, plgpu_colum
     hipStream_t s = as_stream(stream);
     int rc = make_owned_column(out_perm, PLGPU_U32, n, false, s);
     if (rc) return rc;
-    unsigned long long* ctr = nullptr;  // [world] counts, then [world] cursors
-    if ((rc = dev_alloc((void**)&ctr, (size_t)world * 16, s))) {
+    DevBuf<unsigned long long> ctr;  // [world] counts, then [world] cursors
+    if ((rc = ctr.alloc((size_t)world * 16, s))) {
         plgpu_column_release(out_perm);
         return rc;
     }
@@ -3685,7 +3640,6 @@ PLGPU_API int plgpu_gb_route(const plgpu_column* key, int32_t world, plgpu_colum
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);  // `cur` is a host temporary
     }
-    dev_free(ctr, s);
     if (e != hipSuccess) {
         plgpu_column_release(out_perm);
         return hip_fail(e, "gb_route_kernel");
@@ -3727,8 +3681,8 @@ PLGPU_API int plgpu_key_ranges(const plgpu_column* keys, int32_t nkeys, int64_t*
         mk.c[i] = to_dev(keys[i]);
     }
     hipStream_t s = as_stream(stream);
-    unsigned long long* st = nullptr;
-    int rc = dev_alloc((void**)&st, 3 * kMaxKeys * 8, s);
+    DevBuf<unsigned long long> st;
+    int rc = st.alloc(3 * kMaxKeys * 8, s);
     if (rc) return rc;
     unsigned long long h[3 * kMaxKeys];
     for (int i = 0; i < kMaxKeys; ++i) h[3 * i] = ~0ull, h[3 * i + 1] = 0, h[3 * i + 2] = 0;
@@ -3740,7 +3694,6 @@ PLGPU_API int plgpu_key_ranges(const plgpu_column* keys, int32_t nkeys, int64_t*
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, st, sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(st, s);
     if (e != hipSuccess) return hip_fail(e, "key range pass");
     // signed min / max (no valid value: min = INT64_MAX > max = INT64_MIN)
     for (int i = 0; i < nkeys; ++i) {
@@ -3944,29 +3897,24 @@ static int gb_merge_impl(const void* records, int64_t n_records, int32_t nsrc, c
         }
     }
     // source table on the device: nsrc + 1 starts, then nsrc x kMaxAcc shifts
-    int64_t* dsrc = nullptr;
+    DevBuf<int64_t> dsrc;
     if (nsrc > 0) {
         const size_t bytes = (size_t)(nsrc + 1) * 8 + shift.size() * 4;
-        if ((rc = dev_alloc((void**)&dsrc, bytes, R.s))) return rc;
+        if ((rc = dsrc.alloc(bytes, R.s))) return rc;
         std::vector<uint8_t> h(bytes);
         std::memcpy(h.data(), start.data(), (size_t)(nsrc + 1) * 8);
         std::memcpy(h.data() + (size_t)(nsrc + 1) * 8, shift.data(), shift.size() * 4);
         hipError_t e = hipMemcpyAsync(dsrc, h.data(), bytes, hipMemcpyHostToDevice, R.s);
         if (e == hipSuccess) e = hipStreamSynchronize(R.s);  // `h` is a host temporary
-        if (e != hipSuccess) {
-            dev_free(dsrc, R.s);
-            return hip_fail(e, "merge sources");
-        }
+        if (e != hipSuccess) return hip_fail(e, "merge sources");
     }
     for (R.attempts = 0;; ++R.attempts) {
         if ((rc = gb_alloc_table(R))) break;
         // wide sums: zeroed digit arrays for this table
         for (int a = 0; a < kMaxAcc && !rc; ++a) {
             if (!((R.wide >> a) & 1u)) continue;
-            dev_free(R.wide_digits[a], R.s);
-            R.wide_digits[a] = nullptr;
             const size_t words = (size_t)(p.gcap + 2) * wide_nwords(R.wide_exmin[a], R.wide_exmax[a]);
-            rc = dev_alloc((void**)&R.wide_digits[a], words * 8, R.s);
+            rc = R.wide_digits[a].alloc(words * 8, R.s);  // (frees the last attempt's first)
             if (!rc && hipMemsetAsync(R.wide_digits[a], 0, words * 8, R.s) != hipSuccess)
                 rc = fail(PLGPU_ERR_HIP, "wide digits");
         }
@@ -3998,11 +3946,11 @@ static int gb_merge_impl(const void* records, int64_t n_records, int32_t nsrc, c
         }
         R.gbits += 3;
     }
-    dev_free(dsrc, R.s);
+    dsrc.reset();  // (before the sums and the outputs are allocated)
     for (int a = 0; a < kMaxAcc && !rc; ++a) {
         // the merged digits, rounded once per group
         if (!((R.wide >> a) & 1u)) continue;
-        rc = dev_alloc((void**)&R.wide_sum[a], (size_t)(p.gcap + 2) * 8, R.s);
+        rc = R.wide_sum[a].alloc((size_t)(p.gcap + 2) * 8, R.s);
         if (rc) break;
         const int fg = (int)std::min<int64_t>((p.gcap + 2 + 255) / 256, 256 * 16);
         gb_wide_round_kernel<<<fg, 256, 0, R.s>>>(p, R.wide_exmin[a], wide_nwords(R.wide_exmin[a], R.wide_exmax[a]),
@@ -4185,8 +4133,8 @@ static int gb_multi_packed(const MkKeys& mk, MkPack pk, int64_t n, const plgpu_c
         }
         if (rc) return rc;
     }
-    uint64_t* codes = nullptr;
-    int rc = dev_alloc((void**)&codes, (size_t)std::max<int64_t>(n, 1) * 8 + (checked ? 8 : 0), s);
+    DevBuf<uint64_t> codes;
+    int rc = codes.alloc((size_t)std::max<int64_t>(n, 1) * 8 + (checked ? 8 : 0), s);
     if (rc) return rc;
     if (n > 0) {
         unsigned int* outside = checked ? (unsigned int*)(codes + std::max<int64_t>(n, 1)) : nullptr;
@@ -4202,7 +4150,6 @@ static int gb_multi_packed(const MkKeys& mk, MkPack pk, int64_t n, const plgpu_c
         if (e == hipSuccess && outside) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "mk_pack_kernel");
         if (!rc && bad) {
-            dev_free(codes, s);
             *repack = true;
             return PLGPU_OK;
         }
@@ -4224,7 +4171,7 @@ static int gb_multi_packed(const MkKeys& mk, MkPack pk, int64_t n, const plgpu_c
         if (!rc && info) gb_fill_info(R, info);
         if (!rc) rc = gb_finalize(R, naggs, &hout, out_aggs);
     }
-    dev_free(codes, s);
+    codes.reset();  // (before the decoded key columns are allocated)
     if (rc) return rc;
     return gb_multi_decode(pk, keys, nkeys, hout, out_keys, out_aggs, naggs, s);
 }
@@ -4395,10 +4342,10 @@ static int gb_multi_impl(const plgpu_column* keys, int32_t nkeys, const plgpu_co
         if (pk.ok) return gb_multi_packed(mk, pk, n, keys, nkeys, cols, ncols, deriv, program, n_instr, aggs, naggs,
                                           maintain_order, out_keys, out_aggs, info, stream);
     }
-    uint64_t* hashes = nullptr;
-    uint32_t* collision = nullptr;
-    int rc = dev_alloc((void**)&hashes, (size_t)std::max<int64_t>(n, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&collision, 4, s);
+    DevBuf<uint64_t> hashes;
+    DevBuf<uint32_t> collision;
+    int rc = hashes.alloc((size_t)std::max<int64_t>(n, 1) * 8, s);
+    if (!rc) rc = collision.alloc(4, s);
     plgpu_column hk;
     std::memset(&hk, 0, sizeof hk);
     hk.dtype = PLGPU_I64;
@@ -4420,21 +4367,21 @@ static int gb_multi_impl(const plgpu_column* keys, int32_t nkeys, const plgpu_co
         if (!rc) rc = gb_main(R, true, nullptr, nullptr);
         if (rc) break;
         plgpu_column hout;
-        uint64_t* first = nullptr;
+        DevBuf<uint64_t> first;
         if ((rc = gb_finalize(R, naggs, &hout, out_aggs, &first))) break;
         const int64_t groups = hout.length;
         plgpu_column_release(&hout);
         uint32_t coll = 0;
         if (n > 0 && groups > 0) {
             const int64_t total = R.pl.p.gcap + 2;
-            uint64_t* vw = nullptr;
-            if ((rc = dev_alloc((void**)&vw, (size_t)total * (nkeys * 8 + 4), s))) break;
+            DevBuf<uint64_t> vw;
+            if ((rc = vw.alloc((size_t)total * (nkeys * 8 + 4), s))) break;
             uint32_t* vmask = (uint32_t*)(vw + (size_t)total * nkeys);
             (void)hipMemsetAsync(collision, 0, 4, s);
             mk_rep_kernel<<<(unsigned)std::min<int64_t>((total + 255) / 256, 4096), 256, 0, s>>>(R.pl.p, mk, vw,
                                                                                                vmask);
             mk_verify_kernel<<<std::max(hg, 1), 256, 0, s>>>(R.pl.p, mk, hashes, n, vw, vmask, collision);
-            dev_free(vw, s);
+            vw.reset();
             e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(&coll, collision, 4, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -4445,7 +4392,7 @@ static int gb_multi_impl(const plgpu_column* keys, int32_t nkeys, const plgpu_co
             for (int i = 0; i < nkeys && !rc; ++i) {
                 const bool nullable = keys[i].validity != nullptr;
                 if (keys[i].dtype == PLGPU_STR) {  // each group's key string from its first row
-                    rc = str_gather(mk.c[i], nullptr, (const int64_t*)first, nullptr, 0, groups, nullable,
+                    rc = str_gather(mk.c[i], nullptr, (const int64_t*)first.get(), nullptr, 0, groups, nullable,
                                     &out_keys[i], s);
                     continue;
                 }
@@ -4468,12 +4415,9 @@ static int gb_multi_impl(const plgpu_column* keys, int32_t nkeys, const plgpu_co
             }
             done = !rc;
         }
-        dev_free(first, s);
         if (!done)
             for (int i = 0; i < naggs; ++i) plgpu_column_release(&out_aggs[i]);
     }
-    dev_free(collision, s);
-    dev_free(hashes, s);
     if (!rc && !done) rc = fail(PLGPU_ERR_CAPACITY, "multi-key group-by: unresolved 64-bit hash collisions");
     if (rc)
         for (int i = 0; i < nkeys; ++i) plgpu_column_release(&out_keys[i]);
@@ -4782,11 +4726,10 @@ PLGPU_API int plgpu_group_sq_dev(const plgpu_column* row_key, const plgpu_column
     int bits = 6;
     while (((int64_t)1 << bits) < 2 * ng) ++bits;
     const size_t slots = (size_t)1 << bits;
-    uint64_t* tkey = nullptr;
-    uint32_t* tidx = nullptr;
+    DevBuf<uint64_t> tkey;
+    DevBuf<uint32_t> tidx;
     // the library's stream-ordered cache, like every other scratch buffer
-    if ((rc = dev_alloc((void**)&tkey, slots * 16, s)) || (rc = dev_alloc((void**)&tidx, slots * 4 + 12, s))) {
-        dev_free(tkey, s);
+    if ((rc = tkey.alloc(slots * 16, s)) || (rc = tidx.alloc(slots * 4 + 12, s))) {
         plgpu_column_release(out);
         return rc;
     }
@@ -4810,8 +4753,6 @@ PLGPU_API int plgpu_group_sq_dev(const plgpu_column* row_key, const plgpu_column
         }
         e = hipGetLastError();
     }
-    dev_free(tkey, s);
-    dev_free(tidx, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
         plgpu_column_release(out);

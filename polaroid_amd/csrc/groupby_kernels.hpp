@@ -1911,19 +1911,6 @@ struct OutSpec {
     uint32_t* validity;
 };
 
-inline int num_cus() {
-    static int g_num_cus = 0;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            g_num_cus = prop.multiProcessorCount;
-        else
-            g_num_cus = 256;
-    }
-    return g_num_cus;
-}
-
 struct Plan {
     GbParams p;
     std::vector<OutSpec> outs;
@@ -1932,8 +1919,8 @@ struct Plan {
     size_t lds_bytes;
     int grid;
     bool use_lds;
-    bool sum_only;
-    int limbs;         // SUMONLY: 40-bit LDS limbs per f64 sum (3, or 2 for narrow exponent spans)
+    bool sum_only = false;
+    int limbs = 3;     // SUMONLY: 40-bit LDS limbs per f64 sum (3, or 2 for narrow exponent spans)
     int fast_grid;
     bool runs;         // sampled keys mostly equal their next row's (sorted / clustered input)
     bool local;        // range-local mode: contiguous tiles per workgroup, LDS sized by range-local keys

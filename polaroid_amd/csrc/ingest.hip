@@ -72,24 +72,22 @@ __global__ __launch_bounds__(256) void place_bits_kernel(uint64_t* __restrict__ 
 
 int place_bits(uint8_t* dst, int64_t dst_bit, const uint8_t* host_bits, int64_t src_bit, int64_t n, hipStream_t s) {
     if (n <= 0) return PLGPU_OK;
-    uint8_t* tmp = nullptr;
+    DevBuf<uint8_t> tmp;
     int src_rem = 0;
     if (host_bits) {
         const int64_t b0 = src_bit >> 3;
         const int64_t nbytes = ((src_bit + n + 7) >> 3) - b0;
-        int rc = dev_alloc((void**)&tmp, (size_t)nbytes + 16, s);
+        int rc = tmp.alloc((size_t)nbytes + 16, s);
         if (rc) return rc;
-        rc = h2d_staged(tmp, host_bits + b0, (size_t)nbytes, s);
-        if (rc) { dev_free(tmp, s); return rc; }
+        if ((rc = h2d_staged(tmp, host_bits + b0, (size_t)nbytes, s))) return rc;
         src_rem = (int)(src_bit & 7);
     }
     const int64_t words = ((dst_bit + n - 1) >> 6) - (dst_bit >> 6) + 1;
     const int g = (int)std::min<int64_t>((words + 255) / 256, 4096);
     place_bits_kernel<<<g, 256, 0, s>>>((uint64_t*)dst, dst_bit, tmp, src_rem, n);
     const hipError_t e = hipGetLastError();
-    dev_free(tmp, s);  // stream-ordered: the block is reused only by later work
     if (e != hipSuccess) return hip_fail(e, "place_bits_kernel");
-    return PLGPU_OK;
+    return PLGPU_OK;  // tmp is freed stream-ordered: the block is reused only by later work
 }
 
 // offsets[i] += delta for i in [0, n)

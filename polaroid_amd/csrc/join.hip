@@ -813,19 +813,6 @@ __global__ __launch_bounds__(kJnThreads) void jn_probe_emit_kernel(int64_t np, J
     }
 }
 
-
-static int num_cus_jn() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                ? prop.multiProcessorCount
-                : 256;
-    }
-    return n;
-}
-
 // --------------------------------------------------------------- gather
 // `iv` (optional): validity of the index column (Arrow bits from `ioff`); a
 // null index gathers a null (IdxCa::with_nullable_idx + take in the
@@ -1003,7 +990,7 @@ __global__ __launch_bounds__(256) void aos_gather_kernel(const uint64_t* __restr
 template <int NC>
 static hipError_t aos_run(const AosCols& c, int64_t rows, const uint32_t* idx, int64_t n, uint64_t* aos,
                           hipStream_t s) {
-    const int g = std::max(1, num_cus_jn() * 16);
+    const int g = std::max(1, num_cus() * 16);
     {
         KtScope kt("aos_pack_kernel", s);
         aos_pack_kernel<NC><<<g, 256, 0, s>>>(c, rows, aos);
@@ -1050,7 +1037,7 @@ static int gather_into(const plgpu_column& src, const uint32_t* idx, int64_t n, 
     c.offset = src.offset;
     c.values = src.values;
     c.validity = src.validity;
-    const int g = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)num_cus_jn() * 16);
+    const int g = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)num_cus() * 16);
     uint64_t* ov = (uint64_t*)out->validity;
     if (src.dtype == PLGPU_BOOL)
         gather_bool_kernel<<<g, 256, 0, s>>>(c, idx, n, (uint64_t*)out->values, ov, iv, ioff);
@@ -1067,30 +1054,25 @@ static int gather_into(const plgpu_column& src, const uint32_t* idx, int64_t n, 
     return PLGPU_OK;
 }
 
-static int log2_ceil64(int64_t x) {
-    int b = 0;
-    while ((int64_t(1) << b) < x) ++b;
-    return b;
-}
-
 }  // namespace plgpu
 
 using namespace plgpu;
 
-// Built hash table of one join side (kept for the probe).
+// Built hash table of one join side (kept for the probe).  `t` is the
+// kernels' view: its pointers are those of the three buffers owned here.
 struct JnBuilt {
     JnTable t;
+    DevBuf<uint4> cells;
+    DevBuf<uint32_t> off, rowlist;
     uint64_t max_count = 0;
     int64_t rows = 0;
     JnBuilt() { std::memset(&t, 0, sizeof t); }
+    int alloc_cells(int64_t ne, hipStream_t s) {
+        const int rc = cells.alloc(ne * 16, s);
+        t.cells = cells;
+        return rc;
+    }
 };
-
-static void jn_free(JnBuilt& b, hipStream_t s) {
-    dev_free(b.t.cells, s);
-    dev_free(b.t.off, s);
-    dev_free(b.t.rows, s);
-    std::memset(&b.t, 0, sizeof b.t);
-}
 
 static DevCol as_dev(const plgpu_column* c) { return dev_col(*c); }
 
@@ -1098,22 +1080,20 @@ static DevCol as_dev(const plgpu_column* c) { return dev_col(*c); }
 static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnBuilt* out, hipStream_t s) {
     const int64_t nb = key->length;
     const DevCol bk = as_dev(key);
-    int bits = std::max(10, log2_ceil64((nb * 5 + 2) / 3));  // load <= 0.6
-    uint32_t* cnt = nullptr;
-    uint32_t* bslot = nullptr;
-    uint64_t* off64 = nullptr;
-    uint64_t* part = nullptr;
-    unsigned long long* status = nullptr;
-    int rc = dev_alloc((void**)&status, 16, s);
-    if (!rc) rc = dev_alloc((void**)&bslot, std::max<int64_t>(nb, 1) * 4, s);
+    int bits = std::max(10, log2_ceil((nb * 5 + 2) / 3));  // load <= 0.6
+    DevBuf<uint32_t> cnt, bslot;
+    DevBuf<uint64_t> off64, part;
+    DevBuf<unsigned long long> status;
+    int rc = status.alloc(16, s);
+    if (!rc) rc = bslot.alloc(std::max<int64_t>(nb, 1) * 4, s);
     JnBuilt b;
     for (int attempt = 0; !rc; ++attempt) {
         b.t.bits = bits;
         b.t.bbits = bits - 3;
         b.t.cap = int64_t(1) << bits;
         const int64_t ne = b.t.cap + 2;
-        if ((rc = dev_alloc((void**)&b.t.cells, ne * 16, s))) break;
-        if ((rc = dev_alloc((void**)&cnt, ne * 4, s))) break;
+        if ((rc = b.alloc_cells(ne, s))) break;
+        if ((rc = cnt.alloc(ne * 4, s))) break;
         PLGPU_HIP(hipMemsetAsync(status, 0, 16, s));
         const int gi = (int)std::min<int64_t>((ne + 255) / 256, 256 * 32);
         jn_init_kernel<<<gi, 256, 0, s>>>(b.t, cnt);
@@ -1130,17 +1110,17 @@ static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnB
             rc = fail(PLGPU_ERR_CAPACITY, "join build table did not converge");
             break;
         }
-        dev_free(b.t.cells, s);
-        dev_free(cnt, s);
-        b.t.cells = nullptr;
-        cnt = nullptr;
+        b.cells.reset();
+        cnt.reset();
         bits += 2;
     }
     const int64_t ne = b.t.cap + 2;
-    if (!rc) rc = dev_alloc((void**)&b.t.off, (ne + 1) * 4, s);
-    if (!rc) rc = dev_alloc((void**)&off64, (ne + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&part, ((ne + kScanChunk - 1) / kScanChunk + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&b.t.rows, std::max<int64_t>(nb, 1) * 4, s);
+    if (!rc) rc = b.off.alloc((ne + 1) * 4, s);
+    if (!rc) rc = off64.alloc((ne + 1) * 8, s);
+    if (!rc) rc = part.alloc(((ne + kScanChunk - 1) / kScanChunk + 1) * 8, s);
+    if (!rc) rc = b.rowlist.alloc(std::max<int64_t>(nb, 1) * 4, s);
+    b.t.off = b.off;
+    b.t.rows = b.rowlist;
     if (!rc) {
         hipError_t e = scan_exclusive<uint32_t>(cnt, ne, off64, part, s);
         const int ge = (int)std::min<int64_t>((ne + 256) / 256, 256 * 32);
@@ -1162,9 +1142,9 @@ static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnB
     }
     if (!rc && ordered && b.max_count > 1) {
         // deterministic build-row order inside each duplicate key
-        uint32_t* long_slots = nullptr;
+        DevBuf<uint32_t> long_slots;
         unsigned long long* nlong = status;  // reuse word 0
-        rc = dev_alloc((void**)&long_slots, ne * 4, s);
+        rc = long_slots.alloc(ne * 4, s);
         if (!rc) {
             (void)hipMemsetAsync(nlong, 0, 8, s);
             const int ge = (int)std::min<int64_t>((ne + 255) / 256, 256 * 32);
@@ -1178,7 +1158,6 @@ static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnB
             }
             if (e != hipSuccess) rc = hip_fail(e, "join list sort");
         }
-        dev_free(long_slots, s);
     }
     if (!rc) {
         const int ge = (int)std::min<int64_t>((ne + 255) / 256, 256 * 32);
@@ -1186,17 +1165,9 @@ static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnB
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "join build refs");
     }
-    dev_free(cnt, s);
-    dev_free(bslot, s);
-    dev_free(off64, s);
-    dev_free(part, s);
-    dev_free(status, s);
-    if (rc) {
-        jn_free(b, s);
-        return rc;
-    }
+    if (rc) return rc;
     b.rows = nb;
-    *out = b;
+    *out = std::move(b);
     return PLGPU_OK;
 }
 
@@ -1204,7 +1175,7 @@ static int jn_build(const plgpu_column* key, bool nulls_equal, bool ordered, JnB
 // payload columns (jn_build_wide_kernel); *unique = false (and nothing
 // built) when a key repeats.  cells: (cap + 2) 32-B cells.
 struct WideBuilt {
-    WideCell* cells = nullptr;
+    DevBuf<WideCell> cells;
     int64_t cap = 0;
     int bbits = 0;
 };
@@ -1212,9 +1183,9 @@ struct WideBuilt {
 static int jn_build_wide(const plgpu_column* key, const plgpu_column* pays, int W, bool nulls_equal, WideBuilt* out,
                          bool* unique, hipStream_t s) {
     const int64_t nb = key->length;
-    int bits = std::max(10, log2_ceil64((nb * 5 + 2) / 3));  // load <= 0.6
-    unsigned long long* status = nullptr;
-    int rc = dev_alloc((void**)&status, 32, s);
+    int bits = std::max(10, log2_ceil((nb * 5 + 2) / 3));  // load <= 0.6
+    DevBuf<unsigned long long> status;
+    int rc = status.alloc(32, s);
     *unique = true;
     WidePay wp;
     std::memset(&wp, 0, sizeof wp);
@@ -1224,7 +1195,7 @@ static int jn_build_wide(const plgpu_column* key, const plgpu_column* pays, int 
         b.cap = int64_t(1) << bits;
         b.bbits = bits - 2;  // 4 cells per bucket
         const int64_t ne = b.cap + 2;
-        if ((rc = dev_alloc((void**)&b.cells, ne * sizeof(WideCell), s))) break;
+        if ((rc = b.cells.alloc(ne * sizeof(WideCell), s))) break;
         hipError_t e = hipMemsetAsync(status, 0, 32, s);
         if (e == hipSuccess) e = hipMemsetAsync(b.cells, 0x00, ne * sizeof(WideCell), s);
         if (e == hipSuccess) {
@@ -1258,17 +1229,11 @@ static int jn_build_wide(const plgpu_column* key, const plgpu_column* pays, int 
             rc = fail(PLGPU_ERR_CAPACITY, "join build table did not converge");
             break;
         }
-        dev_free(b.cells, s);
-        b.cells = nullptr;
+        b.cells.reset();
         bits += 2;
     }
-    dev_free(status, s);
-    if (rc || !*unique) {
-        dev_free(b.cells, s);
-        b.cells = nullptr;
-        return rc;
-    }
-    *out = b;
+    if (rc || !*unique) return rc;
+    *out = std::move(b);
     return PLGPU_OK;
 }
 
@@ -1277,9 +1242,9 @@ static int jn_build_wide(const plgpu_column* key, const plgpu_column* pays, int 
 static int jn_build_rowformat(const plgpu_column* key, const plgpu_column* pay, bool nulls_equal, JnBuilt* out,
                               bool* unique, hipStream_t s) {
     const int64_t nb = key->length;
-    int bits = std::max(10, log2_ceil64((nb * 5 + 2) / 3));  // load <= 0.6
-    unsigned long long* status = nullptr;
-    int rc = dev_alloc((void**)&status, 32, s);
+    int bits = std::max(10, log2_ceil((nb * 5 + 2) / 3));  // load <= 0.6
+    DevBuf<unsigned long long> status;
+    int rc = status.alloc(32, s);
     *unique = true;
     JnBuilt b;
     for (int attempt = 0; !rc; ++attempt) {
@@ -1287,7 +1252,7 @@ static int jn_build_rowformat(const plgpu_column* key, const plgpu_column* pay, 
         b.t.bbits = bits - 3;
         b.t.cap = int64_t(1) << bits;
         const int64_t ne = b.t.cap + 2;
-        if ((rc = dev_alloc((void**)&b.t.cells, ne * 16, s))) break;
+        if ((rc = b.alloc_cells(ne, s))) break;
         hipError_t e = hipMemsetAsync(status, 0, 32, s);
         // keys EMPTY everywhere; special cells all zero (unoccupied)
         if (e == hipSuccess) e = hipMemsetAsync(b.t.cells, 0x00, ne * 16, s);
@@ -1318,51 +1283,36 @@ static int jn_build_rowformat(const plgpu_column* key, const plgpu_column* pay, 
             rc = fail(PLGPU_ERR_CAPACITY, "join build table did not converge");
             break;
         }
-        dev_free(b.t.cells, s);
-        b.t.cells = nullptr;
+        b.cells.reset();
         bits += 2;
     }
-    dev_free(status, s);
-    if (rc || !*unique) {
-        jn_free(b, s);
-        return rc;
-    }
+    if (rc || !*unique) return rc;
     b.rows = nb;
-    *out = b;
+    *out = std::move(b);
     return PLGPU_OK;
 }
 
 // One probe pass: per-row match words, per-tile output counts and their
 // exclusive scan; `total` output rows.
 struct JnPass {
-    uint32_t* m = nullptr;
-    uint64_t* tcount = nullptr;
-    uint64_t* toff = nullptr;
-    uint64_t* part = nullptr;
+    DevBuf<uint64_t> part, toff, tcount;
+    DevBuf<uint32_t> m;
     int64_t np = 0;
     int64_t ntiles = 0;
     uint64_t total = 0;
 };
 
-static void jn_pass_free(JnPass& p, hipStream_t s) {
-    dev_free(p.m, s);
-    dev_free(p.tcount, s);
-    dev_free(p.toff, s);
-    dev_free(p.part, s);
-    p = JnPass();
-}
-
 static int jn_pass_alloc(int64_t np, JnPass* p, hipStream_t s) {
     p->np = np;
     p->ntiles = std::max<int64_t>(1, (np + kJnTileRows - 1) / kJnTileRows);
-    int rc = dev_alloc((void**)&p->tcount, p->ntiles * 8, s);
-    if (!rc) rc = dev_alloc((void**)&p->toff, (p->ntiles + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&p->part, ((p->ntiles + kScanChunk - 1) / kScanChunk + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&p->m, std::max<int64_t>(np, 1) * 4, s);
+    int rc = p->tcount.alloc(p->ntiles * 8, s);
+    if (!rc) rc = p->toff.alloc((p->ntiles + 1) * 8, s);
+    if (!rc) rc = p->part.alloc(((p->ntiles + kScanChunk - 1) / kScanChunk + 1) * 8, s);
+    if (!rc) rc = p->m.alloc(std::max<int64_t>(np, 1) * 4, s);
     return rc;
 }
 
-static int jn_pass_grid(const JnPass& p) { return (int)std::min<int64_t>(p.ntiles, (int64_t)num_cus_jn() * 8); }
+static int jn_pass_grid(const JnPass& p) { return (int)std::min<int64_t>(p.ntiles, (int64_t)num_cus() * 8); }
 
 // Scan of the tile counts -> p->total (host).
 static int jn_pass_scan(JnPass* p, hipStream_t s, const char* what) {
@@ -1445,7 +1395,7 @@ __global__ __launch_bounds__(256) void jn_idx_validity_kernel(const uint32_t* __
 
 static int jn_idx_validity(plgpu_column* c, hipStream_t s) {
     if (c->validity == nullptr || c->length == 0) return PLGPU_OK;
-    const int g = (int)std::min<int64_t>((c->length + 255) / 256, (int64_t)num_cus_jn() * 16);
+    const int g = (int)std::min<int64_t>((c->length + 255) / 256, (int64_t)num_cus() * 16);
     jn_idx_validity_kernel<<<g, 256, 0, s>>>((const uint32_t*)c->values, c->length, (uint64_t*)c->validity);
     PLGPU_HIP(hipGetLastError());
     return PLGPU_OK;
@@ -1603,7 +1553,6 @@ static int join_impl(const plgpu_column* left_key, const plgpu_column* right_key
         int r2 = jn_build(right_side ? right_key : left_key, neq, false, &o, s);
         if (r2) return r2;
         *unique = o.max_count <= 1;
-        jn_free(o, s);
         return PLGPU_OK;
     };
     bool ok = true;
@@ -1613,18 +1562,15 @@ static int join_impl(const plgpu_column* left_key, const plgpu_column* right_key
     if (!rc && !ok)
         rc = fail(PLGPU_ERR_SCHEMA, validate == PLGPU_JOIN_VALIDATE_1_1 ? "join keys did not fulfill 1:1 validation"
                                                                         : "join keys did not fulfill m:1 validation");
-    if (rc) {
-        jn_free(b, s);
-        return rc;
-    }
+    if (rc) return rc;
     const plgpu_column* pkey = build_right ? left_key : right_key;
     const plgpu_column* bkey = build_right ? right_key : left_key;
     plgpu_column* op = build_right ? out_left_idx : out_right_idx;
     plgpu_column* ob = build_right ? out_right_idx : out_left_idx;
-    uint8_t* flags = nullptr;
+    DevBuf<uint8_t> flags;
     JnPass pp, dp;
     if (drain) {
-        rc = dev_alloc((void**)&flags, b.t.cap + 2, s);
+        rc = flags.alloc(b.t.cap + 2, s);
         if (!rc && hipMemsetAsync(flags, 0, b.t.cap + 2, s) != hipSuccess) rc = fail(PLGPU_ERR_HIP, "join flags");
     }
     if (!rc) rc = jn_match(pkey, b, neq, mode, drain, flags, &pp, s);
@@ -1649,10 +1595,6 @@ static int join_impl(const plgpu_column* left_key, const plgpu_column* right_key
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "join emit");
     }
-    jn_pass_free(pp, s);
-    jn_pass_free(dp, s);
-    dev_free(flags, s);
-    jn_free(b, s);
     if (rc) {
         plgpu_column_release(out_left_idx);
         plgpu_column_release(out_right_idx);
@@ -1679,7 +1621,6 @@ static int jn_select_rows(const plgpu_column& li, const plgpu_column& ri, bool s
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "join semi/anti select");
     }
-    jn_pass_free(p, s);
     if (rc) plgpu_column_release(out);
     return rc;
 }
@@ -1744,15 +1685,19 @@ static void jn_take_emit(const JnPass& pp, const TakeCols& lc, const TakePay& tp
                          hipStream_t s) {
     KtScope kt("jn_take_emit_kernel", s);
     if (W == 1)
-        jn_take_emit_kernel<NC, 1><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m, tp, pp.toff,
+        jn_take_emit_kernel<NC, 1><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m.get(), tp, pp.toff,
                                                                            pp.ntiles, lc, out_idx);
     else if (W == 2)
-        jn_take_emit_kernel<NC, 2><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m, tp, pp.toff,
+        jn_take_emit_kernel<NC, 2><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m.get(), tp, pp.toff,
                                                                            pp.ntiles, lc, out_idx);
     else
-        jn_take_emit_kernel<NC, 3><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m, tp, pp.toff,
+        jn_take_emit_kernel<NC, 3><<<jn_pass_grid(pp), kJnThreads, 0, s>>>(pp.np, (const uint64_t*)pp.m.get(), tp, pp.toff,
                                                                            pp.ntiles, lc, out_idx);
 }
+
+// jn_take_emit<lc.n> (defined after jn_radix_take).
+static void jn_take_emit_cols(const JnPass& pp, const TakeCols& lc, const TakePay& tp, int W, uint32_t* out_idx,
+                              hipStream_t s);
 
 // ------------------------------------------------ partitioned join (round 6)
 // The order-free inner join + take of BASELINE configs[3] (one unique-keyed
@@ -2032,12 +1977,12 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
     // misses it saves (1e7 keys: 2^8 partitions of ~39k keys)
     if (pbits > 8 && (nb >> 8) <= 2 * per && options().join_radix_keys <= 0) pbits = 8;
     const int P = 1 << pbits;
-    const int cus = num_cus_jn();
+    const int cus = num_cus();
     const DevCol bk = as_dev(right_key), bp = as_dev(right_pay);
-    uint32_t* cnt = nullptr;
-    unsigned long long* status = nullptr;  // build flags
-    int rc = dev_alloc((void**)&cnt, (size_t)P * 4, s);
-    if (!rc) rc = dev_alloc((void**)&status, 4 * 8, s);
+    DevBuf<uint32_t> cnt;
+    DevBuf<unsigned long long> status;  // build flags
+    int rc = cnt.alloc((size_t)P * 4, s);
+    if (!rc) rc = status.alloc(4 * 8, s);
     std::vector<uint32_t> hc((size_t)P);
     if (!rc) {
         hipError_t e = hipMemsetAsync(cnt, 0, (size_t)P * 4, s);
@@ -2051,14 +1996,14 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "rj_count_kernel");
     }
-    dev_free(cnt, s);
+    cnt.reset();
     uint32_t maxc = 0;
     for (uint32_t c : hc) maxc = std::max(maxc, c);
     const int load = options().join_radix_load > 0 ? std::min(90, options().join_radix_load) : 35;
     const uint32_t nbk = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)maxc * 100 + 4 * load - 1) / (4 * load)));
-    uint4* cells = nullptr;
+    DevBuf<uint4> cells;
     const int64_t ncells = (int64_t)P * nbk * 4;
-    if (!rc) rc = dev_alloc((void**)&cells, (size_t)ncells * 16, s);
+    if (!rc) rc = cells.alloc((size_t)ncells * 16, s);
     if (!rc) {
         rj_init_kernel<<<(unsigned)std::min<int64_t>((ncells + 255) / 256, cus * 16), 256, 0, s>>>(cells, ncells);
         if (nb > 0) {
@@ -2073,16 +2018,11 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
         if (e != hipSuccess) rc = hip_fail(e, "rj_build_kernel");
         if (!rc && (hs[0] || hs[1] || hs[2])) {
             // duplicate / INT64_MIN build keys: the row-format join decides
-            dev_free(cells, s);
-            dev_free(status, s);
             return PLGPU_OK;
         }
     }
-    dev_free(status, s);
-    if (rc) {
-        dev_free(cells, s);
-        return rc;
-    }
+    status.reset();
+    if (rc) return rc;
     RjTable tab;
     tab.cells = cells;
     tab.nbk = nbk;
@@ -2092,22 +2032,22 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
     rc = radix_partition8(as_dev(left_key), carry, nc, np, pbits, s, &parts);
     // match pass (hit words, packed payloads, tile counts) and its scan
     JnPass pp;
-    uint64_t* mp = nullptr;
+    DevBuf<uint64_t> mp;
     if (!rc) rc = jn_pass_alloc(np, &pp, s);
-    if (!rc) rc = dev_alloc((void**)&mp, (size_t)std::max<int64_t>(np, 1) * 8, s);
+    if (!rc) rc = mp.alloc((size_t)std::max<int64_t>(np, 1) * 8, s);
     if (!rc && hipMemsetAsync(pp.tcount, 0, (size_t)pp.ntiles * 8, s) != hipSuccess)
         rc = fail(PLGPU_ERR_HIP, "rj_match_kernel tile counts");
     if (!rc) {
         KtScope kt("rj_match_kernel", s);
         const unsigned grid = (unsigned)(((2 * pp.ntiles + kRjGroups - 1) / kRjGroups) * kRjGroups);
-        unsigned long long* tc = (unsigned long long*)pp.tcount;
+        unsigned long long* tc = (unsigned long long*)pp.tcount.get();
         // 4 probe steps in flight per wave: 54 VGPRs, the LDS bound of 6
         // workgroups per CU (7.69 ms against 7.96 for 8 steps at 86 VGPRs,
         // 1e9 x 1e7, gpurun_out/r06i_*)
         if (options().join_radix_batch == 8)
-            rj_match_kernel<8><<<grid, kJnThreads, 0, s>>>(parts.key, np, pp.ntiles, tab, (uint64_t*)pp.m, mp, tc);
+            rj_match_kernel<8><<<grid, kJnThreads, 0, s>>>(parts.key, np, pp.ntiles, tab, (uint64_t*)pp.m.get(), mp, tc);
         else
-            rj_match_kernel<4><<<grid, kJnThreads, 0, s>>>(parts.key, np, pp.ntiles, tab, (uint64_t*)pp.m, mp, tc);
+            rj_match_kernel<4><<<grid, kJnThreads, 0, s>>>(parts.key, np, pp.ntiles, tab, (uint64_t*)pp.m.get(), mp, tc);
     }
     if (!rc) rc = jn_pass_scan(&pp, s, "rj_match_kernel");
     const int64_t total = (int64_t)pp.total;
@@ -2131,17 +2071,7 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
         tp.dst[0] = (uint64_t*)out_right[0].values;
     }
     if (!rc && total > 0) {
-        switch (lc.n) {
-        case 0: jn_take_emit<0>(pp, lc, tp, 1, nullptr, s); break;
-        case 1: jn_take_emit<1>(pp, lc, tp, 1, nullptr, s); break;
-        case 2: jn_take_emit<2>(pp, lc, tp, 1, nullptr, s); break;
-        case 3: jn_take_emit<3>(pp, lc, tp, 1, nullptr, s); break;
-        case 4: jn_take_emit<4>(pp, lc, tp, 1, nullptr, s); break;
-        case 5: jn_take_emit<5>(pp, lc, tp, 1, nullptr, s); break;
-        case 6: jn_take_emit<6>(pp, lc, tp, 1, nullptr, s); break;
-        case 7: jn_take_emit<7>(pp, lc, tp, 1, nullptr, s); break;
-        default: jn_take_emit<8>(pp, lc, tp, 1, nullptr, s); break;
-        }
+        jn_take_emit_cols(pp, lc, tp, 1, nullptr, s);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "join take emit");
     }
@@ -2156,12 +2086,23 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
         for (int i = 0; i < nleft; ++i) plgpu_column_release(&out_left[i]);
         plgpu_column_release(&out_right[0]);
     }
-    dev_free(mp, s);
-    jn_pass_free(pp, s);
-    dev_free(parts.buf, s);
-    dev_free(parts.range, s);
-    dev_free(cells, s);
     return rc;
+}
+
+// jn_take_emit<lc.n>: one instantiation per number of fused left columns.
+static void jn_take_emit_cols(const JnPass& pp, const TakeCols& lc, const TakePay& tp, int W, uint32_t* out_idx,
+                              hipStream_t s) {
+    switch (lc.n) {
+    case 0: jn_take_emit<0>(pp, lc, tp, W, out_idx, s); break;
+    case 1: jn_take_emit<1>(pp, lc, tp, W, out_idx, s); break;
+    case 2: jn_take_emit<2>(pp, lc, tp, W, out_idx, s); break;
+    case 3: jn_take_emit<3>(pp, lc, tp, W, out_idx, s); break;
+    case 4: jn_take_emit<4>(pp, lc, tp, W, out_idx, s); break;
+    case 5: jn_take_emit<5>(pp, lc, tp, W, out_idx, s); break;
+    case 6: jn_take_emit<6>(pp, lc, tp, W, out_idx, s); break;
+    case 7: jn_take_emit<7>(pp, lc, tp, W, out_idx, s); break;
+    default: jn_take_emit<8>(pp, lc, tp, W, out_idx, s); break;
+    }
 }
 
 // Inner join + take: the left frame's columns and the right frame's columns
@@ -2262,17 +2203,17 @@ PLGPU_API int plgpu_join_inner_take(const plgpu_column* left_key, const plgpu_co
         return rc;
     }
     JnPass pp;
-    uint64_t* mp = nullptr;  // W dense payload arrays of np words
-    uint32_t* idx = nullptr;
+    DevBuf<uint64_t> mp;  // W dense payload arrays of np words
+    DevBuf<uint32_t> idx;
     const int64_t npw = std::max<int64_t>(left_key->length, 1);
     rc = jn_pass_alloc(left_key->length, &pp, s);
-    if (!rc) rc = dev_alloc((void**)&mp, npw * 8 * W, s);
+    if (!rc) rc = mp.alloc(npw * 8 * W, s);
     if (!rc) {
         const DevCol pk = as_dev(left_key);
         const int g = jn_pass_grid(pp);
         {
             KtScope kt("jn_probe_match_kernel", s);
-            uint64_t* mw = reinterpret_cast<uint64_t*>(pp.m);
+            uint64_t* mw = reinterpret_cast<uint64_t*>(pp.m.get());
             uint64_t* m1 = W > 1 ? mp + npw : nullptr;
             uint64_t* m2 = W > 2 ? mp + 2 * npw : nullptr;
             if (W == 1 && pk.validity)
@@ -2323,19 +2264,9 @@ PLGPU_API int plgpu_join_inner_take(const plgpu_column* left_key, const plgpu_co
             tp.dst[q] = (uint64_t*)out_right[q].values;
         }
     }
-    if (!rc && need_idx) rc = dev_alloc((void**)&idx, std::max<int64_t>(total, 1) * 4, s);
+    if (!rc && need_idx) rc = idx.alloc(std::max<int64_t>(total, 1) * 4, s);
     if (!rc && total > 0) {
-        switch (lc.n) {
-        case 0: jn_take_emit<0>(pp, lc, tp, W, idx, s); break;
-        case 1: jn_take_emit<1>(pp, lc, tp, W, idx, s); break;
-        case 2: jn_take_emit<2>(pp, lc, tp, W, idx, s); break;
-        case 3: jn_take_emit<3>(pp, lc, tp, W, idx, s); break;
-        case 4: jn_take_emit<4>(pp, lc, tp, W, idx, s); break;
-        case 5: jn_take_emit<5>(pp, lc, tp, W, idx, s); break;
-        case 6: jn_take_emit<6>(pp, lc, tp, W, idx, s); break;
-        case 7: jn_take_emit<7>(pp, lc, tp, W, idx, s); break;
-        default: jn_take_emit<8>(pp, lc, tp, W, idx, s); break;
-        }
+        jn_take_emit_cols(pp, lc, tp, W, idx, s);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "join take emit");
     }
@@ -2345,11 +2276,6 @@ PLGPU_API int plgpu_join_inner_take(const plgpu_column* left_key, const plgpu_co
         const hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "join (row-format table)");
     }
-    dev_free(idx, s);
-    dev_free(mp, s);
-    jn_pass_free(pp, s);
-    jn_free(b, s);
-    dev_free(wb.cells, s);
     if (rc) release_all();
     else *out_len = total;
     return rc;
@@ -2419,7 +2345,7 @@ PLGPU_API int plgpu_join_multi(const plgpu_column* left_keys, const plgpu_column
         if (rc || (any_str && short_all)) return rc;
     }
     const bool neq = nulls_equal != 0;
-    const int cus = num_cus_jn();
+    const int cus = num_cus();
     {
         // integer keys whose common ranges fit 63 bits: both sides packed into
         // one exact Int64 key (a tuple with a null is a null key unless
@@ -2428,9 +2354,9 @@ PLGPU_API int plgpu_join_multi(const plgpu_column* left_keys, const plgpu_column
         int rc = mk_plan_pack(ka, nl, &kb, nr, cus * 16, &pk, s);
         if (rc) return rc;
         if (pk.ok) {
-            uint64_t *cl = nullptr, *cr = nullptr;
-            rc = dev_alloc((void**)&cl, (std::max<int64_t>(nl, 1) + (nl + 63) / 64 + 1) * 8, s);
-            if (!rc) rc = dev_alloc((void**)&cr, (std::max<int64_t>(nr, 1) + (nr + 63) / 64 + 1) * 8, s);
+            DevBuf<uint64_t> cl, cr;
+            rc = cl.alloc((std::max<int64_t>(nl, 1) + (nl + 63) / 64 + 1) * 8, s);
+            if (!rc) rc = cr.alloc((std::max<int64_t>(nr, 1) + (nr + 63) / 64 + 1) * 8, s);
             uint64_t* vl = cl ? cl + std::max<int64_t>(nl, 1) : nullptr;
             uint64_t* vr = cr ? cr + std::max<int64_t>(nr, 1) : nullptr;
             if (!rc)
@@ -2457,19 +2383,17 @@ PLGPU_API int plgpu_join_multi(const plgpu_column* left_keys, const plgpu_column
                 a.null_count = b.null_count = neq ? 0 : -1;
                 rc = join_impl(&a, &b, how, neq, maintain_order, validate, out_left_idx, out_right_idx, s);
             }
-            dev_free(cl, s);
-            dev_free(cr, s);
             (void)hipStreamSynchronize(s);
             return rc;
         }
     }
-    uint64_t *hl = nullptr, *hr = nullptr, *vl = nullptr, *vr = nullptr;
-    uint32_t* bad = nullptr;
-    int rc = dev_alloc((void**)&hl, std::max<int64_t>(nl, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&hr, std::max<int64_t>(nr, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&vl, ((nl + 63) / 64 + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&vr, ((nr + 63) / 64 + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&bad, 4, s);
+    DevBuf<uint64_t> hl, hr, vl, vr;
+    DevBuf<uint32_t> bad;
+    int rc = hl.alloc(std::max<int64_t>(nl, 1) * 8, s);
+    if (!rc) rc = hr.alloc(std::max<int64_t>(nr, 1) * 8, s);
+    if (!rc) rc = vl.alloc(((nl + 63) / 64 + 1) * 8, s);
+    if (!rc) rc = vr.alloc(((nr + 63) / 64 + 1) * 8, s);
+    if (!rc) rc = bad.alloc(4, s);
     plgpu_column cl, cr;
     std::memset(&cl, 0, sizeof cl);
     std::memset(&cr, 0, sizeof cr);
@@ -2480,8 +2404,8 @@ PLGPU_API int plgpu_join_multi(const plgpu_column* left_keys, const plgpu_column
     cr.values = hr;
     // null tuples are dropped through the key validity (nulls_equal: every
     // tuple is a value, nulls included, and no validity is needed)
-    cl.validity = neq ? nullptr : (const uint8_t*)vl;
-    cr.validity = neq ? nullptr : (const uint8_t*)vr;
+    cl.validity = neq ? nullptr : (const uint8_t*)vl.get();
+    cr.validity = neq ? nullptr : (const uint8_t*)vr.get();
     cl.null_count = cr.null_count = neq ? 0 : -1;
     bool done = false;
     int validation_fails = 0;
@@ -2533,11 +2457,12 @@ PLGPU_API int plgpu_join_multi(const plgpu_column* left_keys, const plgpu_column
             plgpu_column_release(out_right_idx);
         }
     }
-    dev_free(hl, s);
-    dev_free(hr, s);
-    dev_free(vl, s);
-    dev_free(vr, s);
-    dev_free(bad, s);
+    // back to the pool before the semi / anti selection allocates
+    hl.reset();
+    hr.reset();
+    vl.reset();
+    vr.reset();
+    bad.reset();
     if (!rc && !done) rc = fail(PLGPU_ERR_CAPACITY, "multi-key join: unresolved 64-bit hash collisions");
     if (!rc && rows_only) {
         plgpu_column rows;
@@ -2592,13 +2517,12 @@ PLGPU_API int plgpu_gather(const plgpu_column* cols, int32_t ncols, const plgpu_
             c.dst[k] = (uint64_t*)out_cols[packed[g0 + k]].values;
             done[packed[g0 + k]] = true;
         }
-        uint64_t* aos = nullptr;
-        if (!rc) rc = dev_alloc((void**)&aos, (size_t)rows * ((nc + 1) & ~1) * 8, s);
+        DevBuf<uint64_t> aos;
+        if (!rc) rc = aos.alloc((size_t)rows * ((nc + 1) & ~1) * 8, s);
         if (!rc) {
             hipError_t e = aos_dispatch(nc, c, rows, ix, n, aos, s);
             if (e != hipSuccess) rc = hip_fail(e, "packed gather");
         }
-        dev_free(aos, s);
     }
     for (int i = 0; i < ncols && rc == PLGPU_OK; ++i)
         if (!done[i]) rc = gather_into(cols[i], ix, n, &out_cols[i], s, idx->validity, idx->offset);
@@ -2643,7 +2567,7 @@ PLGPU_API int plgpu_coalesce(const plgpu_column* a, const plgpu_column* b, plgpu
     int rc = make_owned_column(out, a->dtype, n, true, s);
     if (rc) return rc;
     if (n > 0) {
-        const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus_jn() * 16);
+        const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus() * 16);
         coalesce_kernel<<<g, 256, 0, s>>>(as_dev(a), as_dev(b), n, (void*)out->values, (uint64_t*)out->validity);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -2689,7 +2613,7 @@ PLGPU_API int plgpu_join_inner_take_multi(const plgpu_column* left_keys, const p
         kb.c[i] = as_dev(&right_keys[i]);
     }
     const bool neq = nulls_equal != 0;
-    const int cus = num_cus_jn();
+    const int cus = num_cus();
     MkPack pk;
     pk.ok = false;
     if (packable && nl < 0xFFFFFFFFll && nr < 0xFFFFFFFFll) {
@@ -2697,9 +2621,9 @@ PLGPU_API int plgpu_join_inner_take_multi(const plgpu_column* left_keys, const p
         if (rc) return rc;
     }
     if (pk.ok) {
-        uint64_t *cl = nullptr, *cr = nullptr;
-        int rc = dev_alloc((void**)&cl, (std::max<int64_t>(nl, 1) + (nl + 63) / 64 + 1) * 8, s);
-        if (!rc) rc = dev_alloc((void**)&cr, (std::max<int64_t>(nr, 1) + (nr + 63) / 64 + 1) * 8, s);
+        DevBuf<uint64_t> cl, cr;
+        int rc = cl.alloc((std::max<int64_t>(nl, 1) + (nl + 63) / 64 + 1) * 8, s);
+        if (!rc) rc = cr.alloc((std::max<int64_t>(nr, 1) + (nr + 63) / 64 + 1) * 8, s);
         uint64_t* vl = cl ? cl + std::max<int64_t>(nl, 1) : nullptr;
         uint64_t* vr = cr ? cr + std::max<int64_t>(nr, 1) : nullptr;
         if (!rc)
@@ -2728,8 +2652,6 @@ PLGPU_API int plgpu_join_inner_take_multi(const plgpu_column* left_keys, const p
                                        validate, out_left, out_right, out_len, stream);
         }
         (void)hipStreamSynchronize(s);
-        dev_free(cl, s);
-        dev_free(cr, s);
         return rc;
     }
     // pairs (hashed and verified), then the takes

@@ -121,6 +121,75 @@ struct KtScope {
 int dev_alloc(void** p, size_t bytes, hipStream_t s);
 void dev_free(void* p, hipStream_t s);
 
+// Scoped owner of one dev_alloc block: every piece of device scratch is held
+// by one of these, so PLGPU_HIP / an early return never leaks a pool block.
+// The destructor frees on the stream of the allocation; reset() is the
+// explicit early free (a buffer that is handed back before a later
+// allocation of the same function so the pool can reuse the block), and
+// release() hands the pointer to a new owner (OwnedBuffers, an out-parameter).
+template <typename T>
+class DevBuf {
+    T* p_ = nullptr;
+    hipStream_t s_ = nullptr;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), s_(o.s_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            s_ = o.s_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+
+    // Frees what it held, then allocates `bytes`; returns the library's rc.
+    int alloc(size_t bytes, hipStream_t s) {
+        reset();
+        s_ = s;
+        void* v = nullptr;
+        const int rc = dev_alloc(&v, bytes, s);
+        p_ = (T*)v;
+        return rc;
+    }
+    void reset() {
+        if (p_) dev_free(p_, s_);
+        p_ = nullptr;
+    }
+    T* release() {
+        T* r = p_;
+        p_ = nullptr;
+        return r;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+
+// Compute units of the current device (256 where the query fails).
+inline int num_cus() {
+    static int g_num_cus = 0;
+    if (g_num_cus == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+            g_num_cus = prop.multiProcessorCount;
+        else
+            g_num_cus = 256;
+    }
+    return g_num_cus;
+}
+
+inline int log2_ceil(int64_t x) {
+    int b = 0;
+    while ((int64_t(1) << b) < x) ++b;
+    return b;
+}
+
 // A library-owned device column buffer set (released via plgpu_column.release).
 struct OwnedBuffers {
     void* values = nullptr;
@@ -168,14 +237,14 @@ struct DevCol {
 // Radix partition of null-free 8-byte columns by the top `bits` bits of
 // part_hash(key) (groupby.hip gb_partition: count, scan and LDS-staged
 // scatter passes; one pass up to 2^8 partitions, two above): partition q
-// holds rows [hrange[q], hrange[q + 1]) of `key` and of each col[i].  `buf`
-// and `range` (the P + 1 bounds on the device, at `bounds`) are owned by the
-// caller (dev_free).  Used by the join's partitioned probe.
+// holds rows [hrange[q], hrange[q + 1]) of `key` and of each col[i], which
+// point into `buf`; `range` holds the P + 1 bounds on the device, at
+// `bounds`.  Used by the join's partitioned probe.
 struct RadixParts {
-    uint64_t* buf = nullptr;
+    DevBuf<uint64_t> buf;
     uint64_t* key = nullptr;
     uint64_t* col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t* range = nullptr;
+    DevBuf<uint64_t> range;
     const uint64_t* bounds = nullptr;
     std::vector<uint64_t> hrange;
     int levels = 0;

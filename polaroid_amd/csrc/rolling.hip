@@ -1748,15 +1748,14 @@ static int rolling_minmax(const plgpu_column* values, const uint64_t* seg, bool 
     if (rc || p.n == 0) return rc;
     p.out = (void*)out->values;
     p.out_valid = (uint64_t*)out->validity;
-    uint8_t* flags = nullptr;
-    uint64_t* vcount = nullptr;
-    uint64_t* part = nullptr;
+    DevBuf<uint8_t> flags;
+    DevBuf<uint64_t> vcount, part, pre, suf;
     hipError_t e = hipSuccess;
     const unsigned g = (unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 32);
     if (values->validity != nullptr) {
-        rc = dev_alloc((void**)&flags, p.n, s);
-        if (!rc) rc = dev_alloc((void**)&vcount, (p.n + 1) * 8, s);
-        if (!rc) rc = dev_alloc((void**)&part, ((p.n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
+        rc = flags.alloc(p.n, s);
+        if (!rc) rc = vcount.alloc((p.n + 1) * 8, s);
+        if (!rc) rc = part.alloc(((p.n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
         if (!rc) {
             mm_valid_flags_kernel<<<g, 256, 0, s>>>(p.c, p.n, flags);
             e = hipGetLastError();
@@ -1770,8 +1769,10 @@ static int rolling_minmax(const plgpu_column* values, const uint64_t* seg, bool 
         else mm_direct_kernel<true><<<(unsigned)std::min<int64_t>((p.n + kMmTile - 1) / kMmTile, 256 * 64), 256, 0, s>>>(p);
         e = hipGetLastError();
     } else if (!rc && e == hipSuccess && w > kMmDirect) {
-        rc = dev_alloc((void**)&p.pre, p.n * 8, s);
-        if (!rc) rc = dev_alloc((void**)&p.suf, p.n * 8, s);
+        rc = pre.alloc(p.n * 8, s);
+        if (!rc) rc = suf.alloc(p.n * 8, s);
+        p.pre = pre;
+        p.suf = suf;
         if (!rc) {
             const int64_t nb = (p.n + w - 1) / w;  // one wave (of 4 per workgroup) per block
             mm_blocks_kernel<<<(unsigned)std::min<int64_t>((nb + 3) / 4, 256 * 64), 256, 0, s>>>(p);
@@ -1787,26 +1788,9 @@ static int rolling_minmax(const plgpu_column* values, const uint64_t* seg, bool 
     }
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) rc = hip_fail(e, "rolling min / max");
-    dev_free(flags, s);
-    dev_free(vcount, s);
-    dev_free(part, s);
-    dev_free(p.pre, s);
-    dev_free(p.suf, s);
     if (rc) plgpu_column_release(out);
     else out->null_count = -1;
     return rc;
-}
-
-static int num_cus_rl() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                ? prop.multiProcessorCount
-                : 256;
-    }
-    return n;
 }
 
 // The segmented launches of the wave family (w <= kRwMaxW), per input dtype:
@@ -1869,31 +1853,24 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
     // the bitmap as 8-byte words from bit 0: the column's own buffer where
     // it is laid out so (as plgpu_segment_starts writes it), else a copy
     const uint64_t* seg = nullptr;
-    uint64_t* seg_own = nullptr;
+    DevBuf<uint64_t> seg_own;
     if (segd && values->length > 0) {
         const uintptr_t at = (uintptr_t)seg_starts->values + (uintptr_t)(seg_starts->offset / 8);
         if (seg_starts->offset % 8 == 0 && at % 8 == 0) {
             seg = (const uint64_t*)at;
         } else {
             const int64_t words = (values->length + 63) / 64;
-            int rc = dev_alloc((void**)&seg_own, (size_t)words * 8, s);
+            int rc = seg_own.alloc((size_t)words * 8, s);
             if (rc) return rc;
             seg_repack_kernel<<<(unsigned)std::min<int64_t>((words * 64 + 255) / 256, 256 * 64), 256, 0, s>>>(
                 dev_col(*seg_starts), values->length, seg_own);
             const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) {
-                dev_free(seg_own, s);
-                return hip_fail(e, "segment starts");
-            }
+            if (e != hipSuccess) return hip_fail(e, "segment starts");
             seg = seg_own;
         }
     }
-    if (kind == PLGPU_ROLLING_MIN || kind == PLGPU_ROLLING_MAX) {
-        const int rc = rolling_minmax(values, seg, kind == PLGPU_ROLLING_MAX, window_size, min_periods, center != 0,
-                                      out, s);
-        dev_free(seg_own, s);
-        return rc;
-    }
+    if (kind == PLGPU_ROLLING_MIN || kind == PLGPU_ROLLING_MAX)
+        return rolling_minmax(values, seg, kind == PLGPU_ROLLING_MAX, window_size, min_periods, center != 0, out, s);
     RlSegParams p;  // (the plain kernels take its RlParams part)
     std::memset(&p, 0, sizeof p);
     p.seg = seg;
@@ -1921,10 +1898,8 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
     p.out_int = (!p.mean && !var && !p.isf) ? values->dtype : 0;
     const int32_t odt = p.out_int ? values->dtype : PLGPU_F64;
     int rc = make_owned_column(out, odt, p.n, true, s);
-    if (rc || p.n == 0) {
-        dev_free(seg_own, s);
-        return rc;
-    }
+    if (rc || p.n == 0) return rc;
+    DevBuf<uint32_t> rest;
     p.out = (void*)out->values;
     p.out_valid = (uint64_t*)out->validity;
     const int64_t tiles = (p.n + kRlOut - 1) / kRlOut;
@@ -1939,18 +1914,17 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
             // the common blocks by rl_var_hot_kernel, the rest listed for
             // rl_var_rest_kernel (stream-ordered; the count read on the device)
             const int64_t nblocks = (p.n + kRwOut - 1) / kRwOut;
-            int arc = dev_alloc((void**)&p.rest, (size_t)(nblocks + 1) * 4, s);
+            int arc = rest.alloc((size_t)(nblocks + 1) * 4, s);
+            p.rest = rest;
             if (!arc && hipMemsetAsync(p.rest, 0, 4, s) != hipSuccess) arc = PLGPU_ERR_HIP;
             if (arc) {
-                if (p.rest) dev_free(p.rest, s);
-                dev_free(seg_own, s);
                 plgpu_column_release(out);
                 return arc == PLGPU_ERR_HIP ? hip_fail(hipGetLastError(), "rolling") : arc;
             }
             const bool st = options().rl_stream != 0;
             const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
-            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus_rl() * per_cu));
-            const unsigned gr = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus_rl()));
+            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus() * per_cu));
+            const unsigned gr = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus()));
 #define PLGPU_RLHOT(DT)                                                      \
     do {                                                                     \
         if (mhot) {                                                          \
@@ -1979,7 +1953,7 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
         } else if (!nl && options().rl_stream != 0) {
             // null-free: resident waves streaming their blocks
             const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
-            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus_rl() * per_cu));
+            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus() * per_cu));
             if (values->dtype == PLGPU_F64) {
                 if (var) rl_stream_kernel<PLGPU_F64, true><<<gs, 64 * kRwWaves, 0, s>>>(p);
                 else rl_stream_kernel<PLGPU_F64, false><<<gs, 64 * kRwWaves, 0, s>>>(p);
@@ -2028,8 +2002,6 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
         rl_direct_kernel<false><<<(unsigned)std::min<int64_t>((p.n + 255) / 256, 256 * 64), 256, 0, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (p.rest) dev_free(p.rest, s);
-    dev_free(seg_own, s);
     if (e != hipSuccess) {
         plgpu_column_release(out);
         return hip_fail(e, "rolling");

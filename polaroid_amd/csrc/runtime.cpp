@@ -298,16 +298,16 @@ static void release_owned(plgpu_column* c) {
 int make_owned_column(plgpu_column* out, int32_t dtype, int64_t length, bool with_validity,
                       hipStream_t s) {
     std::memset(out, 0, sizeof *out);
-    OwnedBuffers* ob = new OwnedBuffers();
-    ob->stream = s;
     size_t vbytes = dtype == PLGPU_BOOL ? (size_t)((length + 63) / 64) * 8
                                         : (size_t)length * dtype_bytes(dtype);
-    int rc = dev_alloc(&ob->values, vbytes, s);
-    if (rc != PLGPU_OK) { delete ob; return rc; }
-    if (with_validity) {
-        rc = dev_alloc(&ob->validity, (size_t)((length + 63) / 64) * 8, s);
-        if (rc != PLGPU_OK) { dev_free(ob->values, s); delete ob; return rc; }
-    }
+    DevBuf<void> values, validity;
+    int rc = values.alloc(vbytes, s);
+    if (rc != PLGPU_OK) return rc;
+    if (with_validity && (rc = validity.alloc((size_t)((length + 63) / 64) * 8, s)) != PLGPU_OK) return rc;
+    OwnedBuffers* ob = new OwnedBuffers();
+    ob->stream = s;
+    ob->values = values.release();
+    ob->validity = validity.release();
     int dev = 0;
     (void)hipGetDevice(&dev);
     out->dtype = dtype;

@@ -159,18 +159,6 @@ __global__ __launch_bounds__(256) void sh_pack_bits_kernel(const uint8_t* __rest
     if ((threadIdx.x & 63) == 0 && z) atomicAdd(zeros, (unsigned long long)z);
 }
 
-static int num_cus_sh() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                ? prop.multiProcessorCount
-                : 256;
-    }
-    return n;
-}
-
 static DevCol sh_dev(const plgpu_column& c) {
     DevCol d;
     std::memset(&d, 0, sizeof d);
@@ -211,16 +199,15 @@ PLGPU_API int plgpu_hash_partition(const plgpu_column* keys, int32_t nkeys, int3
     while ((1u << dbits) < P + 1) ++dbits;  // destination codes 0..P (P = dropped)
     const int64_t nwt = std::max<int64_t>(1, (n + kShWaveRows - 1) / kShWaveRows);
     const int64_t ncnt = (int64_t)P * nwt;
-    uint32_t* counts = nullptr;
-    uint64_t* off = nullptr;
-    uint64_t* part = nullptr;
-    int64_t* totals = nullptr;
-    int rc = dev_alloc((void**)&counts, ncnt * 4, s);
-    if (!rc) rc = dev_alloc((void**)&off, (ncnt + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&part, ((ncnt + kScanChunk - 1) / kScanChunk + 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&totals, (int64_t)P * 8, s);
+    DevBuf<uint32_t> counts;
+    DevBuf<uint64_t> off, part;
+    DevBuf<int64_t> totals;
+    int rc = counts.alloc(ncnt * 4, s);
+    if (!rc) rc = off.alloc((ncnt + 1) * 8, s);
+    if (!rc) rc = part.alloc(((ncnt + kScanChunk - 1) / kScanChunk + 1) * 8, s);
+    if (!rc) rc = totals.alloc((int64_t)P * 8, s);
     const size_t lds = (size_t)kShWaves * P * 4;
-    const int g = (int)std::min<int64_t>((nwt + kShWaves - 1) / kShWaves, (int64_t)num_cus_sh() * 8);
+    const int g = (int)std::min<int64_t>((nwt + kShWaves - 1) / kShWaves, (int64_t)num_cus() * 8);
     int64_t total = 0;
     if (!rc) {
         sh_count_kernel<<<g, kShThreads, lds, s>>>(k, n, P, drop, nwt, counts);
@@ -244,10 +231,6 @@ PLGPU_API int plgpu_hash_partition(const plgpu_column* keys, int32_t nkeys, int3
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "hash partition scatter");
     }
-    dev_free(counts, s);
-    dev_free(off, s);
-    dev_free(part, s);
-    dev_free(totals, s);
     if (rc) plgpu_column_release(out_perm);
     return rc;
 }
@@ -270,7 +253,7 @@ PLGPU_API int plgpu_gather_rows(const plgpu_column* cols, int32_t ncols, const p
         if (n > 0 && dst_values[i] == nullptr) return fail(PLGPU_ERR_INVALID, "NULL destination buffer");
     }
     if (n == 0) return PLGPU_OK;
-    const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus_sh() * 16);
+    const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus() * 16);
     for (int i = 0; i < ncols; ++i) {
         const DevCol c = sh_dev(cols[i]);
         uint8_t* dv = dst_valid ? dst_valid[i] : nullptr;
@@ -293,19 +276,18 @@ PLGPU_API int plgpu_pack_bits(const uint8_t* bytes, int64_t n, uint8_t* out_bits
     hipStream_t s = as_stream(stream);
     if (n < 0) return fail(PLGPU_ERR_INVALID, "negative length");
     if (n > 0 && (bytes == nullptr || out_bits == nullptr)) return fail(PLGPU_ERR_INVALID, "NULL argument");
-    unsigned long long* z = nullptr;
-    int rc = dev_alloc((void**)&z, 8, s);
+    DevBuf<unsigned long long> z;
+    int rc = z.alloc(8, s);
     if (rc) return rc;
     unsigned long long hz = 0;
     hipError_t e = hipMemsetAsync(z, 0, 8, s);
     if (e == hipSuccess && n > 0) {
-        const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus_sh() * 16);
+        const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)num_cus() * 16);
         sh_pack_bits_kernel<<<g, 256, 0, s>>>(bytes, n, (uint64_t*)out_bits, z);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&hz, z, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(z, s);
     if (e != hipSuccess) return hip_fail(e, "pack bits");
     if (out_zero_count) *out_zero_count = (int64_t)hz;
     return PLGPU_OK;

@@ -471,27 +471,17 @@ using namespace plgpu;
 
 // Scratch of the radix passes over n codes.
 struct SrtScratch {
-    uint32_t* cnt = nullptr;  // per-tile digit counts, scanned in place into offsets
-    uint64_t* part = nullptr;
-    unsigned long long* hist = nullptr;
-    uint64_t* tbits = nullptr;  // per-tile OR / AND (srt_codes_stats_kernel)
+    DevBuf<uint32_t> cnt;  // per-tile digit counts, scanned in place into offsets
+    DevBuf<uint64_t> part;
+    DevBuf<unsigned long long> hist;
+    DevBuf<uint64_t> tbits;  // per-tile OR / AND (srt_codes_stats_kernel)
     int alloc(int64_t n, hipStream_t s, bool stats = false) {
         const int64_t ntiles = (n + kSrtTile - 1) / kSrtTile;
-        int rc = dev_alloc((void**)&hist, 16, s);
-        if (!rc && n > 0 && stats) rc = dev_alloc((void**)&tbits, ntiles * 16, s);
-        if (!rc && n > 0) rc = dev_alloc((void**)&cnt, ntiles * 256 * 4, s);
-        if (!rc && n > 0) rc = dev_alloc((void**)&part, ((ntiles * 256 + kScanChunk - 1) / kScanChunk + 1) * 8, s);
+        int rc = hist.alloc(16, s);
+        if (!rc && n > 0 && stats) rc = tbits.alloc(ntiles * 16, s);
+        if (!rc && n > 0) rc = cnt.alloc(ntiles * 256 * 4, s);
+        if (!rc && n > 0) rc = part.alloc(((ntiles * 256 + kScanChunk - 1) / kScanChunk + 1) * 8, s);
         return rc;
-    }
-    void release(hipStream_t s) {
-        dev_free(cnt, s);
-        dev_free(part, s);
-        dev_free(hist, s);
-        dev_free(tbits, s);
-        tbits = nullptr;
-        cnt = nullptr;
-        part = nullptr;
-        hist = nullptr;
     }
 };
 
@@ -519,8 +509,8 @@ static void srt_down(const uint64_t* ki, const uint32_t* ii, int64_t nv, int shi
 // sc.tbits and the byte-0 digit counts in sc.cnt.  final_out (optional): the
 // last pass writes the sorted row ids there (*wrote_final = true) instead of
 // into idx[cur].
-static int radix_passes(uint64_t* keys[2], uint32_t* idx[2], int64_t nv, int& cur, SrtScratch& sc, hipStream_t s,
-                        bool ids_implicit = false, bool pre = false, uint32_t* final_out = nullptr,
+static int radix_passes(DevBuf<uint64_t> keys[2], DevBuf<uint32_t> idx[2], int64_t nv, int& cur, SrtScratch& sc,
+                        hipStream_t s, bool ids_implicit = false, bool pre = false, uint32_t* final_out = nullptr,
                         bool* wrote_final = nullptr) {
     if (wrote_final) *wrote_final = false;
     if (nv <= 0) return PLGPU_OK;
@@ -616,23 +606,22 @@ PLGPU_API int plgpu_arg_sort(const plgpu_column* key, int32_t descending, int32_
     c.validity = key->validity;
     int rc = make_owned_column(out_idx, PLGPU_U32, n, false, s);
     if (rc || n == 0) return rc;
-    uint64_t* keys[2] = {nullptr, nullptr};
-    uint32_t* idx[2] = {nullptr, nullptr};
-    uint32_t* nulls = nullptr;
-    uint64_t* part = nullptr;
+    DevBuf<uint64_t> keys[2];
+    DevBuf<uint32_t> idx[2];
+    DevBuf<uint32_t> nulls;
     const int64_t nblk = (n + 1023) / 1024;
     for (int i = 0; i < 2 && !rc; ++i) {
-        rc = dev_alloc((void**)&keys[i], n * 8, s);
-        if (!rc) rc = dev_alloc((void**)&idx[i], n * 4, s);
+        rc = keys[i].alloc(n * 8, s);
+        if (!rc) rc = idx[i].alloc(n * 4, s);
     }
     int64_t nv = n;  // valid rows
     if (!rc && c.validity) {
-        uint64_t* voff = nullptr;
-        uint32_t* vcnt = nullptr;
-        rc = dev_alloc((void**)&vcnt, nblk * 4, s);
-        if (!rc) rc = dev_alloc((void**)&voff, (nblk + 1) * 8, s);
-        if (!rc) rc = dev_alloc((void**)&part, ((nblk + kScanChunk - 1) / kScanChunk + 1) * 8, s);
-        if (!rc) rc = dev_alloc((void**)&nulls, n * 4, s);
+        DevBuf<uint64_t> voff, part;
+        DevBuf<uint32_t> vcnt;
+        rc = vcnt.alloc(nblk * 4, s);
+        if (!rc) rc = voff.alloc((nblk + 1) * 8, s);
+        if (!rc) rc = part.alloc(((nblk + kScanChunk - 1) / kScanChunk + 1) * 8, s);
+        if (!rc) rc = nulls.alloc(n * 4, s);
         if (!rc) {
             srt_count_valid_kernel<<<(unsigned)nblk, 256, 0, s>>>(c, n, vcnt);
             hipError_t e = scan_exclusive<uint32_t>(vcnt, nblk, voff, part, s);
@@ -646,10 +635,7 @@ PLGPU_API int plgpu_arg_sort(const plgpu_column* key, int32_t descending, int32_
             if (e != hipSuccess) rc = hip_fail(e, "sort prep");
             nv = (int64_t)tv;
         }
-        dev_free(vcnt, s);
-        dev_free(voff, s);
-        dev_free(part, s);
-        part = nullptr;
+        // (vcnt, voff and part go back to the pool here, before the radix scratch is allocated)
     }
     int cur = 0;
     SrtScratch sc;
@@ -671,7 +657,6 @@ PLGPU_API int plgpu_arg_sort(const plgpu_column* key, int32_t descending, int32_
     uint32_t* ndst = nulls_last ? out + nv : out;
     bool wrote = false;
     if (!rc) rc = radix_passes(keys, idx, nv, cur, sc, s, stats, stats, vdst, &wrote);
-    sc.release(s);
     if (!rc) {
         hipError_t e = hipSuccess;
         if (nv > 0 && !wrote) e = hipMemcpyAsync(vdst, idx[cur], nv * 4, hipMemcpyDeviceToDevice, s);
@@ -679,11 +664,6 @@ PLGPU_API int plgpu_arg_sort(const plgpu_column* key, int32_t descending, int32_
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "sort output");
     }
-    for (int i = 0; i < 2; ++i) {
-        dev_free(keys[i], s);
-        dev_free(idx[i], s);
-    }
-    dev_free(nulls, s);
     if (rc) plgpu_column_release(out_idx);
     return rc;
 }
@@ -708,11 +688,11 @@ PLGPU_API int plgpu_arg_sort_multi(const plgpu_column* keys_in, int32_t nkeys, c
     if (n >= 0xFFFFFFFFll) return fail(PLGPU_ERR_CAPACITY, "sort input exceeds the u32 index space");
     int rc = make_owned_column(out_idx, PLGPU_U32, n, false, s);
     if (rc || n == 0) return rc;
-    uint64_t* keys[2] = {nullptr, nullptr};
-    uint32_t* idx[2] = {nullptr, nullptr};
+    DevBuf<uint64_t> keys[2];
+    DevBuf<uint32_t> idx[2];
     for (int i = 0; i < 2 && !rc; ++i) {
-        rc = dev_alloc((void**)&keys[i], n * 8, s);
-        if (!rc) rc = dev_alloc((void**)&idx[i], n * 4, s);
+        rc = keys[i].alloc(n * 8, s);
+        if (!rc) rc = idx[i].alloc(n * 4, s);
     }
     SrtScratch sc;
     if (!rc) rc = sc.alloc(n, s);
@@ -723,13 +703,13 @@ PLGPU_API int plgpu_arg_sort_multi(const plgpu_column* keys_in, int32_t nkeys, c
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "sort iota");
     }
-    unsigned long long* maxlen = nullptr;
+    DevBuf<unsigned long long> maxlen;
     for (int j = nkeys - 1; j >= 0 && !rc; --j) {
         const DevCol c = dev_col(keys_in[j]);
         hipError_t e = hipSuccess;
         if (c.dtype == PLGPU_STR) {
             unsigned long long ml = 0;
-            if (maxlen == nullptr && (rc = dev_alloc((void**)&maxlen, 8, s))) break;
+            if (maxlen == nullptr && (rc = maxlen.alloc(8, s))) break;
             e = hipMemsetAsync(maxlen, 0, 8, s);
             if (e == hipSuccess) {
                 srt_str_maxlen_kernel<<<g, 256, 0, s>>>(c, n, maxlen);
@@ -765,12 +745,6 @@ PLGPU_API int plgpu_arg_sort_multi(const plgpu_column* keys_in, int32_t nkeys, c
         hipError_t e = hipMemcpyAsync((void*)out_idx->values, idx[cur], n * 4, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "sort output");
-    }
-    sc.release(s);
-    dev_free(maxlen, s);
-    for (int i = 0; i < 2; ++i) {
-        dev_free(keys[i], s);
-        dev_free(idx[i], s);
     }
     if (rc) plgpu_column_release(out_idx);
     return rc;
@@ -855,8 +829,8 @@ PLGPU_API int plgpu_segment_starts(const plgpu_column* keys, int32_t nkeys, plgp
         *out_sorted = 1;
         return PLGPU_OK;
     }
-    uint32_t* flag = nullptr;
-    rc = dev_alloc((void**)&flag, 4, s);
+    DevBuf<uint32_t> flag;
+    rc = flag.alloc(4, s);
     uint32_t h = 1;
     hipError_t e = hipSuccess;
     if (!rc) {
@@ -871,7 +845,6 @@ PLGPU_API int plgpu_segment_starts(const plgpu_column* keys, int32_t nkeys, plgp
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "segment starts");
     }
-    dev_free(flag, s);
     if (rc) {
         plgpu_column_release(out_starts);
         return rc;

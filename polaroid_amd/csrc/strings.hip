@@ -115,18 +115,6 @@ __global__ __launch_bounds__(kStrThreads) void str_copy_long_kernel(DevCol src, 
     }
 }
 
-static int num_cus_str() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                ? prop.multiProcessorCount
-                : 256;
-    }
-    return n;
-}
-
 // out = src[idx] for a PLGPU_STR column; idx is UInt32 (idx32) or Int64
 // (idx64) row ids; `iv` / `ioff`: optional index validity (a null index
 // gathers a null).  The output is library-owned.
@@ -134,15 +122,14 @@ int str_gather(const DevCol& src, const uint32_t* idx32, const int64_t* idx64, c
                int64_t n, bool nullable, plgpu_column* out, hipStream_t s) {
     int rc = make_owned_column(out, PLGPU_I64, n + 1, nullable, s);  // offsets (+ validity)
     if (rc) return rc;
-    uint64_t* lens = nullptr;
-    uint64_t* part = nullptr;
-    int64_t* long_rows = nullptr;
-    unsigned long long* nlong = nullptr;
+    DevBuf<uint64_t> lens, part;
+    DevBuf<int64_t> long_rows;
+    DevBuf<unsigned long long> nlong;
     uint64_t total = 0;
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + kStrThreads - 1) / kStrThreads,
-                                                              (int64_t)num_cus_str() * 16));
-    rc = dev_alloc((void**)&lens, std::max<int64_t>(n, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&part, ((n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
+                                                              (int64_t)num_cus() * 16));
+    rc = lens.alloc(std::max<int64_t>(n, 1) * 8, s);
+    if (!rc) rc = part.alloc(((n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
     uint64_t* out_off = (uint64_t*)out->values;
     if (!rc) {
         if (n > 0)
@@ -156,8 +143,8 @@ int str_gather(const DevCol& src, const uint32_t* idx32, const int64_t* idx64, c
     }
     if (!rc) rc = owned_attach_data(out, (int64_t)total, s);
     if (!rc && total > 0) {
-        rc = dev_alloc((void**)&long_rows, n * 8, s);
-        if (!rc) rc = dev_alloc((void**)&nlong, 8, s);
+        rc = long_rows.alloc(n * 8, s);
+        if (!rc) rc = nlong.alloc(8, s);
         unsigned long long hl = 0;
         hipError_t e = hipSuccess;
         if (!rc) {
@@ -171,7 +158,7 @@ int str_gather(const DevCol& src, const uint32_t* idx32, const int64_t* idx64, c
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e == hipSuccess && hl > 0) {
                 const int gl = (int)std::min<int64_t>(((int64_t)hl * 64 + kStrThreads - 1) / kStrThreads,
-                                                      (int64_t)num_cus_str() * 16);
+                                                      (int64_t)num_cus() * 16);
                 str_copy_long_kernel<<<gl, kStrThreads, 0, s>>>(src, idx32, idx64, out_off, (uint8_t*)out->data,
                                                                 long_rows, (int64_t)hl);
                 e = hipGetLastError();
@@ -183,10 +170,6 @@ int str_gather(const DevCol& src, const uint32_t* idx32, const int64_t* idx64, c
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "string gather");
     }
-    dev_free(lens, s);
-    dev_free(part, s);
-    dev_free(long_rows, s);
-    dev_free(nlong, s);
     if (rc) plgpu_column_release(out);
     return rc;
 }
@@ -270,10 +253,10 @@ __global__ __launch_bounds__(kStrThreads) void str_code_bytes_kernel(DevCol code
 int str_short_codes(const plgpu_column& src, plgpu_column* out, bool* all_short, hipStream_t s) {
     const int64_t n = src.length;
     std::memset(out, 0, sizeof *out);
-    uint64_t* codes = nullptr;
-    unsigned long long* flag = nullptr;
-    int rc = dev_alloc((void**)&codes, std::max<int64_t>(n, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&flag, 8, s);
+    DevBuf<uint64_t> codes;
+    DevBuf<unsigned long long> flag;
+    int rc = codes.alloc(std::max<int64_t>(n, 1) * 8, s);
+    if (!rc) rc = flag.alloc(8, s);
     unsigned long long hf = 0;
     if (!rc) {
         int64_t data_end = 0;
@@ -282,7 +265,7 @@ int str_short_codes(const plgpu_column& src, plgpu_column* out, bool* all_short,
             e = hipMemcpyAsync(&data_end, (const int64_t*)src.values + src.offset + n, 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess && n > 0) {
-            const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus_str() * 16);
+            const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus() * 16);
             const bool words = ((uintptr_t)src.data & 7) == 0;
             {
                 KtScope kt("str_code_kernel", s);
@@ -294,11 +277,7 @@ int str_short_codes(const plgpu_column& src, plgpu_column* out, bool* all_short,
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "short-string codes");
     }
-    dev_free(flag, s);
-    if (rc) {
-        dev_free(codes, s);
-        return rc;
-    }
+    if (rc) return rc;
     *all_short = hf == 0;
     // same validity bitmap and offset as the strings: values[offset + r] is
     // the code of row r
@@ -307,8 +286,8 @@ int str_short_codes(const plgpu_column& src, plgpu_column* out, bool* all_short,
     out->offset = src.offset;
     out->null_count = src.null_count;
     out->validity = src.validity;
-    out->values = codes - src.offset;
-    out->private_data = codes;  // the allocation (free with str_codes_free)
+    out->values = codes.get() - src.offset;
+    out->private_data = codes.release();  // the allocation (free with str_codes_free)
     return PLGPU_OK;
 }
 
@@ -322,14 +301,13 @@ int str_from_codes(const plgpu_column& codes, plgpu_column* out, hipStream_t s) 
     const bool nullable = codes.validity != nullptr;
     int rc = make_owned_column(out, PLGPU_I64, n + 1, nullable, s);
     if (rc) return rc;
-    uint64_t* lens = nullptr;
-    uint64_t* part = nullptr;
+    DevBuf<uint64_t> lens, part;
     uint64_t total = 0;
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>((n + kStrThreads - 1) / kStrThreads,
-                                                              (int64_t)num_cus_str() * 16));
+                                                              (int64_t)num_cus() * 16));
     const DevCol dc = dev_col(codes);
-    rc = dev_alloc((void**)&lens, std::max<int64_t>(n, 1) * 8, s);
-    if (!rc) rc = dev_alloc((void**)&part, ((n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
+    rc = lens.alloc(std::max<int64_t>(n, 1) * 8, s);
+    if (!rc) rc = part.alloc(((n + kScanChunk - 1) / kScanChunk + 2) * 8, s);
     uint64_t* out_off = (uint64_t*)out->values;
     if (!rc) {
         if (n > 0) str_code_len_kernel<<<g, kStrThreads, 0, s>>>(dc, n, lens, (uint64_t*)out->validity);
@@ -346,8 +324,6 @@ int str_from_codes(const plgpu_column& codes, plgpu_column* out, hipStream_t s) 
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "codes to strings");
     }
-    dev_free(lens, s);
-    dev_free(part, s);
     if (rc) plgpu_column_release(out);
     return rc;
 }
@@ -458,9 +434,9 @@ PLGPU_API int plgpu_str_compare(const plgpu_column* a, const plgpu_column* b, co
     const int64_t n = a->length;
     int rc = make_owned_column(out, PLGPU_BOOL, n, true, s);
     if (rc || n == 0) return rc;
-    uint8_t* dlit = nullptr;
+    DevBuf<uint8_t> dlit;
     if (!unary && b == nullptr) {
-        rc = dev_alloc((void**)&dlit, std::max<int64_t>(lit_len, 1), s);
+        rc = dlit.alloc(std::max<int64_t>(lit_len, 1), s);
         if (!rc && lit_len > 0 && hipMemcpyAsync(dlit, lit, lit_len, hipMemcpyHostToDevice, s) != hipSuccess)
             rc = fail(PLGPU_ERR_HIP, "string literal upload");
     }
@@ -468,14 +444,13 @@ PLGPU_API int plgpu_str_compare(const plgpu_column* a, const plgpu_column* b, co
         DevCol db;
         std::memset(&db, 0, sizeof db);
         if (b) db = dev_col(*b);
-        const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus_str() * 16);
+        const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus() * 16);
         str_cmp_kernel<<<g, kStrThreads, 0, s>>>(dev_col(*a), db, dlit, lit_len, op, n, (uint64_t*)out->values,
                                                  (uint64_t*)out->validity);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "string comparison");
     }
-    dev_free(dlit, s);
     if (rc) plgpu_column_release(out);
     return rc;
 }
@@ -489,9 +464,9 @@ PLGPU_API int plgpu_str_encode_short(const plgpu_column* strs, plgpu_column* out
     const int64_t n = strs->length;
     int rc = make_owned_column(out_codes, PLGPU_I64, n, strs->validity != nullptr, s);
     if (rc) return rc;
-    unsigned long long* flag = nullptr;
+    DevBuf<unsigned long long> flag;
     unsigned long long hf = 0;
-    rc = dev_alloc((void**)&flag, 8, s);
+    rc = flag.alloc(8, s);
     if (!rc) {
         int64_t data_end = 0;
         hipError_t e = hipMemsetAsync(flag, 0, 8, s);
@@ -499,7 +474,7 @@ PLGPU_API int plgpu_str_encode_short(const plgpu_column* strs, plgpu_column* out
             e = hipMemcpyAsync(&data_end, (const int64_t*)strs->values + strs->offset + n, 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess && n > 0) {
-            const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus_str() * 16);
+            const int g = (int)std::min<int64_t>((n + kStrThreads - 1) / kStrThreads, (int64_t)num_cus() * 16);
             str_code_kernel<<<g, kStrThreads, 0, s>>>(dev_col(*strs), n, (uint64_t*)out_codes->values, flag,
                                                       ((uintptr_t)strs->data & 7) == 0, data_end,
                                                       (uint64_t*)out_codes->validity);
@@ -509,7 +484,6 @@ PLGPU_API int plgpu_str_encode_short(const plgpu_column* strs, plgpu_column* out
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "short-string codes");
     }
-    dev_free(flag, s);
     if (rc) {
         plgpu_column_release(out_codes);
         return rc;

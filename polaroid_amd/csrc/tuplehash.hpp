@@ -390,9 +390,9 @@ inline int mk_plan_pack_sampled(const MkKeys& ka, int64_t na, MkPack* pk, hipStr
         if (dtype_is_float(ka.c[i].dtype) || ka.c[i].dtype == PLGPU_U64 || ka.c[i].dtype == PLGPU_STR)
             return PLGPU_OK;
     if (options().no_pack) return PLGPU_OK;
-    unsigned long long* st = nullptr;
+    DevBuf<unsigned long long> st;
     const size_t bytes = 3 * kMaxKeys * 8;
-    int rc = dev_alloc((void**)&st, bytes, s);
+    int rc = st.alloc(bytes, s);
     if (rc) return rc;
     unsigned long long h[3 * kMaxKeys];
     for (int j = 0; j < kMaxKeys; ++j) h[3 * j] = ~0ull, h[3 * j + 1] = 0, h[3 * j + 2] = 0;
@@ -406,7 +406,6 @@ inline int mk_plan_pack_sampled(const MkKeys& ka, int64_t na, MkPack* pk, hipStr
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, st, bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(st, s);
     if (e != hipSuccess) return hip_fail(e, "sampled key range pass");
     uint64_t r[3 * kMaxKeys];
     for (int i = 0; i < ka.n; ++i) {
@@ -446,9 +445,9 @@ inline int mk_plan_pack(const MkKeys& ka, int64_t na, const MkKeys* kb, int64_t 
         if (dtype_is_float(ka.c[i].dtype) || ka.c[i].dtype == PLGPU_U64 || ka.c[i].dtype == PLGPU_STR)
             return PLGPU_OK;  // hashed path (UInt64 ranges do not fit the signed range pass)
     if (options().no_pack) return PLGPU_OK;  // tests: force the hashed path
-    unsigned long long* st = nullptr;
+    DevBuf<unsigned long long> st;
     const size_t bytes = 2 * 3 * kMaxKeys * 8;
-    int rc = dev_alloc((void**)&st, bytes, s);
+    int rc = st.alloc(bytes, s);
     if (rc) return rc;
     unsigned long long h[2 * 3 * kMaxKeys];
     for (int j = 0; j < 2 * kMaxKeys; ++j) {
@@ -467,7 +466,6 @@ inline int mk_plan_pack(const MkKeys& ka, int64_t na, const MkKeys* kb, int64_t 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, st, bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(st, s);
     if (e != hipSuccess) return hip_fail(e, "key range pass");
     uint64_t r[3 * kMaxKeys];
     for (int i = 0; i < ka.n; ++i) {
