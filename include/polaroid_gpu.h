@@ -843,6 +843,48 @@ int plgpu_rolling_segmented(const plgpu_column* values, const plgpu_column* seg_
                             plgpu_column* out, void* stream);
 int plgpu_invert_permutation(const plgpu_column* idx, plgpu_column* out_idx, void* stream);
 
+/* ---- cumulative and lag functions ----------------------------------------------
+ * plgpu_cumulative: the running sum / minimum / maximum / non-null count of a
+ * column, restarted at every set bit of seg_starts (NULL: one segment; else a
+ * null-free Boolean column of the values' length, as plgpu_segment_starts
+ * writes it).  Replaces polars-ops/src/series/ops/cum_agg.rs cum_sum :340,
+ * cum_min :378, cum_max :416, cum_count :420 (the det_* folds at :14-51) and,
+ * with seg_starts, their evaluation on every group's rows
+ * (polars-expr/src/expressions/window.rs:356, GroupsToRows).  A null row gives
+ * null and leaves the running value as it was.
+ *   SUM    Int32 / Int64 / UInt64 wrap at their width; Float64 is the correctly rounded
+ *          exact sum of the segment's non-null values so far (rounded once; a
+ *          zero sum is +0.0), NaN after a NaN or after both infinities, else
+ *          the infinity that occurred.  PLGPU_ERR_SCHEMA when the column's
+ *          finite non-zero values span more than 67 binades (the fixed-point
+ *          accumulator's window less a significand).  This refusal depends on
+ *          the data, not on the schema: it is found on the device, after the
+ *          launches, and reported with the code the library uses for polars'
+ *          ComputeError (PLGPU_ERR_SCHEMA; plgpu_last_error states the span
+ *          and the limit); no output column is returned.
+ *   MIN / MAX  Int32 / Int64 / UInt64 / Float64, dtype kept; a NaN is skipped once a
+ *          non-NaN value has been seen, before that the output is NaN.
+ *   COUNT  any dtype; UInt32 output without nulls.
+ * Three launches (tile reduce, scan of the tile totals, apply); no workgroup
+ * waits on another.
+ *
+ * plgpu_lag: SHIFT out[i] = values[i - n] (validity with the value) where row
+ * i - n lies in the column and no segment start lies in (i - n, i] (n > 0) or
+ * (i, i - n] (n < 0); elsewhere fill_bits (the value's bits in the column's
+ * dtype) when has_fill, else null.  Replaces ChunkedArray::shift_and_fill.
+ * DIFF out[i] = values[i] - values[i - n] under the same rule (null where
+ * either is; has_fill ignored): one IEEE subtraction for floats, wrapping for
+ * integers.  Replaces polars-ops/src/series/ops/diff.rs:4 with
+ * NullBehavior::Ignore.  4- and 8-byte numeric dtypes (DIFF: signed and float
+ * ones); the output keeps the dtype. */
+enum plgpu_cum_kind { PLGPU_CUM_SUM = 1, PLGPU_CUM_MIN = 2, PLGPU_CUM_MAX = 3, PLGPU_CUM_COUNT = 4 };
+int plgpu_cumulative(const plgpu_column* values, const plgpu_column* seg_starts /* NULL: one segment */,
+                     int32_t kind, plgpu_column* out, void* stream);
+enum plgpu_lag_kind { PLGPU_LAG_SHIFT = 1, PLGPU_LAG_DIFF = 2 };
+int plgpu_lag(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind, int64_t n,
+              int32_t has_fill, int64_t fill_bits /* value bits in the column's dtype */,
+              plgpu_column* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,8 @@ SIGNATURES = {
     "plgpu_segment_starts": (C.c_int, [_COLP, C.c_int32, _COLP, C.POINTER(C.c_int32), _P]),
     "plgpu_rolling_segmented": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _COLP, _P]),
     "plgpu_invert_permutation": (C.c_int, [_COLP, _COLP, _P]),
+    "plgpu_cumulative": (C.c_int, [_COLP, _COLP, C.c_int32, _COLP, _P]),
+    "plgpu_lag": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _COLP, _P]),
 }
 
 GB_MAX_ACC = 6
@@ -199,6 +201,10 @@ JOIN_ORDER = {None: 0, "none": 0, "left": 1, "right": 2, "left_right": 3, "right
 JOIN_VALIDATE = {"m:m": 0, "1:m": 1, "m:1": 2, "1:1": 3}
 JOIN_HOW = {"inner": 0, "left": 1, "right": 2, "full": 3, "semi": 4, "anti": 5}
 ROLLING = {"sum": 1, "mean": 2, "min": 3, "max": 4, "var": 5, "std": 6}
+CUM = {"sum": 1, "min": 2, "max": 3, "count": 4}
+LAG = {"shift": 1, "diff": 2}
+CUM_BLOCK = 2048            # kCumBlock (csrc/cumulative.hip): rows of one workgroup scan
+CUM_TILE = 8 * CUM_BLOCK    # kCumTile: rows per workgroup of the scan kernels (one summary / carry each)
 
 _lib = None
 

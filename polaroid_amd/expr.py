@@ -23,7 +23,7 @@ class Expr:
 
     def __init__(self, kind: str, args: Sequence["Expr"] = (), op: str | None = None,
                  value: Any = None, name: str | None = None):
-        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | over | ...
+        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | over | ...
         self.args = tuple(args)
         self.op = op
         self.value = value
@@ -70,6 +70,10 @@ class Expr:
             return "len()"
         if self.kind == "rolling":
             return f"{self.args[0]!r}.rolling_{self.op}{self.value}"
+        if self.kind == "cum":
+            return f"{self.args[0]!r}.cum_{self.op}()"
+        if self.kind == "lag":
+            return f"{self.args[0]!r}.{self.op}{self.value}"
         if self.kind == "over":
             keys = ", ".join(f'col("{k}")' for k in self.value)
             return f"{self.args[0]!r}.over([{keys}])"
@@ -202,6 +206,10 @@ class Expr:
             raise N.InvalidOperationError(
                 f"{self!r}.{op}(): a window expression (over) inside an aggregation's input is not supported "
                 "on the GPU executor")
+        if _has_cum_lag(self):
+            raise N.InvalidOperationError(
+                f"{self!r}.{op}(): a cumulative or lag function (cum_* / shift / diff) inside an aggregation's "
+                "input is not supported on the GPU executor")
         return Expr("agg", (self,), op=op, value=value)
 
     def sum(self): return self._agg("sum")
@@ -246,14 +254,55 @@ class Expr:
         """Fixed-window standard deviation (Expr.rolling_std)."""
         return _rolling(self, "std", window_size, weights, min_samples, center, ddof)
 
+    # ------------------------------------------------- cumulative / lag
+    def cum_sum(self, *, reverse: bool = False) -> "Expr":
+        """Running sum (Expr.cum_sum): Float64 sums are exact and rounded once."""
+        return _cum(self, "sum", reverse)
+
+    def cum_min(self, *, reverse: bool = False) -> "Expr":
+        """Running minimum (Expr.cum_min; a NaN is skipped once a value has been seen)."""
+        return _cum(self, "min", reverse)
+
+    def cum_max(self, *, reverse: bool = False) -> "Expr":
+        """Running maximum (Expr.cum_max)."""
+        return _cum(self, "max", reverse)
+
+    def cum_count(self, *, reverse: bool = False) -> "Expr":
+        """Running count of non-null rows (Expr.cum_count), UInt32."""
+        return _cum(self, "count", reverse)
+
+    def cum_prod(self, *, reverse: bool = False) -> "Expr":
+        raise N.InvalidOperationError(
+            "cum_prod is not supported on the GPU executor (a running product has no exact fixed-point form)")
+
+    def pct_change(self, n: Any = 1) -> "Expr":
+        raise N.InvalidOperationError(
+            "pct_change is not supported on the GPU executor (it needs forward_fill); "
+            "`x / x.shift(n) - 1` covers the null-free case")
+
+    def shift(self, n: Any = 1, *, fill_value: Any = None) -> "Expr":
+        """Expr.shift with a literal `n` and an optional literal `fill_value`."""
+        _lag_input(self, "shift")
+        return Expr("lag", (self,), op="shift", value=(_lag_n(n, "shift"), _lag_fill(fill_value)))
+
+    def diff(self, n: Any = 1, null_behavior: str = "ignore") -> "Expr":
+        """Expr.diff: x - x.shift(n) (null_behavior "ignore")."""
+        _lag_input(self, "diff")
+        if null_behavior != "ignore":
+            raise N.InvalidOperationError(
+                f"diff(null_behavior={null_behavior!r}) is not supported on the GPU executor: dropping the leading "
+                "nulls changes the length of the column")
+        return Expr("lag", (self,), op="diff", value=(_lag_n(n, "diff"),))
+
     def over(self, partition_by: Any, *more_exprs: Any, order_by: Any = None,
              mapping_strategy: str = "group_to_rows") -> "Expr":
         """Expr.over: evaluate this expression on every group of the partition
         keys, each result back at its row (polars-expr/src/expressions/
         window.rs:356 WindowExpr::evaluate with WindowMapping::GroupsToRows).
-        Takes `<elementwise>.rolling_*(...)` and the aggregations sum / mean /
+        Takes `<elementwise>.rolling_*(...)`, the aggregations sum / mean /
         min / max / count / len / first / last / std / var of an elementwise
-        expression (or pl.len()), over plain key columns."""
+        expression (or pl.len()), and `<elementwise>.cum_*()` / `.shift(...)` /
+        `.diff(...)`, over plain key columns."""
         keys: list[str] = []
         items = [partition_by, *more_exprs]
         while items:
@@ -283,7 +332,7 @@ class Expr:
         f = self
         while f.kind == "alias":
             f = f.args[0]
-        if f.kind == "rolling":
+        if f.kind in ("rolling", "cum", "lag"):
             ok = _is_elementwise(f.args[0])
         elif f.kind == "agg":
             ok = f.op in _OVER_AGGS and _is_elementwise(f.args[0])
@@ -292,7 +341,8 @@ class Expr:
         if not ok:
             raise N.InvalidOperationError(
                 f"{self!r}.over(...): the GPU executor evaluates over groups only rolling_* functions and the "
-                f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression")
+                f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression, "
+                "and cum_sum / cum_min / cum_max / cum_count / shift / diff of an elementwise expression")
         return Expr("over", (self,), op="over", value=tuple(keys))
 
     def sort(self, *, descending: bool = False, nulls_last: bool = False) -> "Expr":
@@ -313,6 +363,63 @@ def _rolling(e: Expr, kind: str, window_size: int, weights, min_samples, center,
     if not 0 <= int(ddof) <= 255:
         raise N.InvalidOperationError("`ddof` must be in 0..255")
     return Expr("rolling", (e,), op=kind, value=(window_size, ms, bool(center), int(ddof)))
+
+
+def _is_rowwise(e: Expr) -> bool:
+    """Elementwise expressions and rolling / cumulative / lag functions of them:
+    one value per row, in row order."""
+    if e.kind == "over":
+        return True
+    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag") and builtins.all(_is_rowwise(a) for a in e.args)
+
+
+def _lag_input(e: Expr, what: str) -> None:
+    if not _is_rowwise(e):
+        raise N.InvalidOperationError(
+            f"{e!r}.{what}(...): the input must be an elementwise expression (not an aggregation or a sort)")
+
+
+def _cum(e: Expr, kind: str, reverse) -> Expr:
+    if reverse:
+        raise N.InvalidOperationError(f"cum_{kind}(reverse=True) is not supported on the GPU executor")
+    _lag_input(e, f"cum_{kind}")
+    return Expr("cum", (e,), op=kind, value=(False,))
+
+
+def _lag_n(n: Any, what: str):
+    """A literal `n`: any integer type (operator.index), or for shift a
+    literal null, which shifts every row out (an all-null column)."""
+    import operator
+
+    if isinstance(n, Expr) and n.kind == "lit":
+        n = n.value
+    if n is None:
+        if what != "shift":
+            raise N.InvalidOperationError(f"{what}(n=None): `n` must be an integer")
+        return None
+    if isinstance(n, Expr):
+        raise N.InvalidOperationError(
+            f"{what}(n={n!r}): a computed `n` is not supported on the GPU executor (pass an integer)")
+    try:
+        if isinstance(n, bool):
+            raise TypeError
+        return operator.index(n)
+    except TypeError:
+        raise N.InvalidOperationError(f"{what}(n={n!r}): `n` must be an integer") from None
+
+
+def _lag_fill(v: Any):
+    if isinstance(v, Expr):
+        if v.kind != "lit":
+            raise N.InvalidOperationError(
+                f"shift(fill_value={v!r}): a computed `fill_value` is not supported on the GPU executor "
+                "(pass a scalar or lit)")
+        v = v.value
+    return v
+
+
+def _has_cum_lag(e: Expr) -> bool:
+    return e.kind in ("cum", "lag") or builtins.any(_has_cum_lag(a) for a in e.args)
 
 
 _OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")

@@ -16,7 +16,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _native as N
-from .expr import Expr, _has_over, col, lit, lower, to_instr_array
+from .expr import Expr, _has_cum_lag, _has_over, _lag_n, col, lit, lower, to_instr_array
 
 
 # ------------------------------------------------------------------ dtypes
@@ -636,6 +636,148 @@ class Series:
             raise N.InvalidOperationError("`min_samples` should be <= `window_size`")
         return self._rolling(N.ROLLING["std"], window_size, min_samples, center, ddof)
 
+    # cumulative / lag (Series.cum_*, Series.shift, Series.diff) --------------
+    def _reinterpret(self, dtype: DataType) -> "Series":
+        """The same buffers read as another physical dtype of the same width."""
+        s = Series.__new__(Series)
+        s.name = self.name
+        s._logical = None
+        c = N.Column.from_buffer_copy(self._col)
+        c.dtype = dtype.code
+        c.release = None
+        c.private_data = None
+        s._col = c
+        s._keep = [self]
+        return s
+
+    def _cast_wrap(self, dtype: DataType) -> "Series":
+        """Integer cast that wraps (plgpu_eval of one overflowing CAST)."""
+        return _eval(Expr("cast", (col(self.name),), op="wrap", value=dtype),
+                     DataFrame([self])).alias(self.name)._with_logical(None)
+
+    def _cum(self, kind: str, reverse: bool = False, seg: "Series | None" = None) -> "Series":
+        """Running sum / min / max / count on the device (plgpu_cumulative)
+        over Int32 / Int64 / Float64; the other dtypes as cum_agg.rs takes
+        them: cum_sum of Int8 / Int16 / UInt8 / UInt16 sums as Int64 (:340),
+        of Boolean as UInt32; UInt32 / UInt64 sums wrap at their own width
+        (UInt32 by the Int32 kernel on the same bits); Float32 runs as Float64
+        and is rounded back; min / max keep the dtype.  `seg` (a Boolean column of
+        segment starts, Expr.over): the running value restarts at every start."""
+        if reverse:
+            raise N.InvalidOperationError(f"cum_{kind}(reverse=True) is not supported on the GPU executor")
+
+        def run(src: "Series") -> "Series":
+            out = N.Column()
+            N.check(N.lib().plgpu_cumulative(C.byref(src._col), None if seg is None else C.byref(seg._col),
+                                             N.CUM[kind], C.byref(out), None))
+            return Series._from_native(self.name, out)
+
+        if kind == "count":
+            return run(self)
+        lg = self._logical_dtype()
+        if self.dtype is String:
+            raise N.InvalidOperationError(f"cum_{kind} of a String / Categorical column is not supported")
+        phys = _BY_CODE[self._col.dtype]
+        if kind == "sum":
+            if lg is not None and not isinstance(lg, Duration):
+                raise N.InvalidOperationError(f"cum_sum of a {lg} column is not supported")
+            src = self
+            if phys is Boolean:
+                src, phys = self._cast_to(UInt32), UInt32
+            if phys is UInt32:
+                return run(src._reinterpret(Int32))._reinterpret(UInt32).alias(self.name)
+            if phys in (Int8, Int16, UInt8, UInt16):
+                return run(self._cast_to(Int64))
+            if phys is Float32:
+                return run(self._cast_to(Float64))._cast_to(Float32)
+            return run(self)._with_logical(lg)
+        if phys is Boolean:
+            raise N.InvalidOperationError(f"cum_{kind} of a Boolean column is not supported")
+        if phys in (Int8, Int16, UInt8, UInt16, UInt32):
+            return run(self._cast_to(Int64))._cast_to(phys)
+        if phys is Float32:
+            return run(self._cast_to(Float64))._cast_to(Float32)
+        return run(self)._with_logical(lg)
+
+    def cum_sum(self, *, reverse: bool = False) -> "Series":
+        return self._cum("sum", reverse)
+
+    def cum_min(self, *, reverse: bool = False) -> "Series":
+        return self._cum("min", reverse)
+
+    def cum_max(self, *, reverse: bool = False) -> "Series":
+        return self._cum("max", reverse)
+
+    def cum_count(self, *, reverse: bool = False) -> "Series":
+        return self._cum("count", reverse)
+
+    def _lag(self, op: str, n: int, fill_value: Any = None, seg: "Series | None" = None) -> "Series":
+        """shift / diff on the device (plgpu_lag) over the 4- and 8-byte
+        dtypes; 1- and 2-byte integers run as Int64.  diff's result dtypes are
+        diff.rs:4's: UInt8 -> Int16, UInt16 -> Int32, UInt32 / UInt64 -> Int64,
+        Datetime / Duration -> Duration of the same unit."""
+        n = _lag_n(n, op)
+        if n is None:
+            # shift(None): every row null, the fill ignored (test_shift.py:124); a shift
+            # past the column's end is that column
+            n, fill_value = self.len() + 1, None
+        if isinstance(fill_value, Expr):
+            if fill_value.kind != "lit":
+                raise N.InvalidOperationError(
+                    f"shift(fill_value={fill_value!r}): a computed `fill_value` is not supported on the GPU executor")
+            fill_value = fill_value.value
+        if self.dtype is String or self._col.dtype == N.BOOL:
+            raise N.InvalidOperationError(f"{op} of a {self.dtype} column is not supported on the GPU executor")
+        lg = self._logical_dtype()
+        phys = _BY_CODE[self._col.dtype]
+
+        def run(src: "Series", fill=None) -> "Series":
+            out = N.Column()
+            bits = 0
+            if fill is not None:
+                sp = _BY_CODE[src._col.dtype]
+                if sp in FLOAT_DTYPES:
+                    bits = int(np.array([fill], dtype=sp.np_dtype).view(np.uint64 if sp is Float64 else np.uint32)[0])
+                else:
+                    bits = int(fill) & (0xFFFFFFFFFFFFFFFF if N.DTYPE_BYTES[sp.code] == 8 else 0xFFFFFFFF)
+                if bits >= 1 << 63:
+                    bits -= 1 << 64
+            N.check(N.lib().plgpu_lag(C.byref(src._col), None if seg is None else C.byref(seg._col), N.LAG[op],
+                                      int(n), int(fill is not None), bits, C.byref(out), None))
+            return Series._from_native(self.name, out)
+
+        if op == "shift":
+            fill = fill_value
+            if fill is not None and lg is not None and not isinstance(fill, (int, np.integer)):
+                fill = _temporal_literal(fill, lg)
+            if fill is not None and lg is None and phys in INTEGER_DTYPES and not isinstance(fill, (int, np.integer)):
+                if float(fill) != int(fill):
+                    raise N.InvalidOperationError(f"shift(fill_value={fill!r}) does not fit a {phys} column")
+                fill = int(fill)
+            if phys in (Int8, Int16, UInt8, UInt16):
+                return run(self._cast_to(Int64), fill)._cast_to(phys)
+            return run(self, fill)._with_logical(lg)
+        if lg is not None and not isinstance(lg, (Datetime, Duration)):
+            raise N.InvalidOperationError(f"diff of a {lg} column is not supported on the GPU executor")
+        out_lg = Duration(lg.time_unit) if lg is not None else None
+        if phys in (UInt8, UInt16):
+            return run(self._cast_to(Int64))._cast_to(Int16 if phys is UInt8 else Int32)
+        if phys in (UInt32, UInt64):
+            return run(self._cast_to(Int64))
+        if phys in (Int8, Int16):
+            return run(self._cast_to(Int64))._cast_wrap(phys)
+        return run(self)._with_logical(out_lg)
+
+    def shift(self, n: int = 1, *, fill_value: Any = None) -> "Series":
+        return self._lag("shift", n, fill_value)
+
+    def diff(self, n: int = 1, null_behavior: str = "ignore") -> "Series":
+        if null_behavior != "ignore":
+            raise N.InvalidOperationError(
+                f"diff(null_behavior={null_behavior!r}) is not supported on the GPU executor: dropping the leading "
+                "nulls changes the length of the column")
+        return self._lag("diff", n)
+
     # eager conveniences mirroring Series.filter ------------------------------
     def filter(self, mask: "Series") -> "Series":
         out = (N.Column * 1)()
@@ -944,6 +1086,10 @@ class LazyFrame:
             raise N.InvalidOperationError(
                 "a window expression (over) in a filter predicate is not supported on the GPU executor: "
                 "compute it with with_columns first and filter on that column")
+        if _has_cum_lag(pred):
+            raise N.InvalidOperationError(
+                "a cumulative or lag function (cum_* / shift / diff) in a filter predicate is not supported on the "
+                "GPU executor: compute it with with_columns first and filter on that column")
         return LazyFrame(("filter", self._node, pred))
 
     def group_by(self, *by: Any, maintain_order: bool = False) -> "LazyGroupBy":
@@ -1425,6 +1571,26 @@ def _over_rolling(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | Non
     return vals.gather(idx_s)._rolling(kind, w, ms, center, ddof, seg=starts).gather(inv)
 
 
+def _cum_lag(f: Expr, vals: Series, seg: Series | None = None) -> Series:
+    """A "cum" / "lag" node on its evaluated input."""
+    if f.kind == "cum":
+        return vals._cum(f.op, f.value[0], seg=seg)
+    return vals._lag(f.op, f.value[0], f.value[1] if f.op == "shift" else None, seg=seg)
+
+
+def _over_cum_lag(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
+    """<elementwise>.cum_*() / .shift(...) / .diff(...).over(keys), routed as
+    _over_rolling: presorted keys cost the segment starts and one kernel,
+    otherwise sort, gather, kernel and the gather back."""
+    vals = _eval(f.args[0], df, cache)
+    starts, idx_s, inv = _over_segments(keys, df, cache)
+    if starts.len() != vals.len():
+        raise N.ShapeError("over(): the partition keys and the values differ in length")
+    if idx_s is None:
+        return _cum_lag(f, vals, starts)
+    return _cum_lag(f, vals.gather(idx_s), starts).gather(inv)
+
+
 def _over_agg(f: Expr, keys: Sequence[str], df: DataFrame) -> Series:
     """<aggregation>.over(keys): group_by(keys, maintain_order=True).agg(f)
     left-joined back on the keys with nulls_equal, in row order -- the
@@ -1442,7 +1608,16 @@ def _over_agg(f: Expr, keys: Sequence[str], df: DataFrame) -> Series:
     return out["__over_agg"]
 
 
-def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list) -> Expr:
+def _cum_lag_below(e: Expr, top: bool = True) -> bool:
+    """Is a cum / lag node anywhere but at the top (under its alias) of e?"""
+    if e.kind == "alias":
+        return _cum_lag_below(e.args[0], top)
+    if e.kind in ("cum", "lag") and not top:
+        return True
+    return builtins.any(_cum_lag_below(a, False) for a in e.args)
+
+
+def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list, top: bool = True) -> Expr:
     """(A module-level function, not a closure of _lower_overs: a recursive
     closure is a reference cycle that would keep `extra`, and with it every
     materialised result column, alive until the cycle collector runs.)"""
@@ -1450,22 +1625,34 @@ def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list) -> Expr:
         f = e.args[0]
         while f.kind == "alias":
             f = f.args[0]
-        res = _over_rolling(f, e.value, df, cache) if f.kind == "rolling" else _over_agg(f, e.value, df)
+        if f.kind == "rolling":
+            res = _over_rolling(f, e.value, df, cache)
+        elif f.kind in ("cum", "lag"):
+            res = _over_cum_lag(f, e.value, df, cache)
+        else:
+            res = _over_agg(f, e.value, df)
+        name = f"__over{builtins.len(extra)}"
+        extra.append(res.alias(name))
+        return col(name)
+    if e.kind in ("cum", "lag") and not top:
+        # inside a larger expression (x / x.shift(1) - 1): a temporary column too
+        res = _cum_lag(e, _eval(e.args[0], df, cache))
         name = f"__over{builtins.len(extra)}"
         extra.append(res.alias(name))
         return col(name)
     if not e.args:
         return e
-    args = tuple(_over_walk(a, df, cache, extra) for a in e.args)
+    args = tuple(_over_walk(a, df, cache, extra, top and e.kind == "alias") for a in e.args)
     if builtins.all(x is y for x, y in zip(args, e.args)):
         return e
     return Expr(e.kind, args, op=e.op, value=e.value, name=e._name)
 
 
 def _lower_overs(expr: Expr, df: DataFrame, cache: dict | None = None) -> tuple[Expr, DataFrame]:
-    """Materialise every over(...) sub-expression as a temporary column (as
-    _lower_strings does for String comparisons) and replace it by that
-    column, so the rest of the expression evaluates as usual."""
+    """Materialise every over(...) sub-expression (and every cum / lag node
+    below the top of the expression) as a temporary column (as _lower_strings
+    does for String comparisons) and replace it by that column, so the rest
+    of the expression evaluates as usual."""
     extra: list[Series] = []
     new = _over_walk(expr, df, cache, extra)
     return new, DataFrame(list(df._cols.values()) + extra)
@@ -1474,7 +1661,7 @@ def _lower_overs(expr: Expr, df: DataFrame, cache: dict | None = None) -> tuple[
 def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
     """`overs`: what the over() nodes of one select / with_columns share
     (_over_segments), valid for this `df` alone."""
-    if _has_over(expr):
+    if _has_over(expr) or _cum_lag_below(expr):
         name = expr.output_name()
         expr, df = _lower_overs(expr, df, overs)
         return _eval(expr, df).alias(name)
@@ -1491,6 +1678,8 @@ def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
         else:
             res = inner.sort(descending=base.value[0], nulls_last=base.value[1])
         return res.alias(expr.output_name())
+    if base.kind in ("cum", "lag"):
+        return _cum_lag(base, _eval(base.args[0], df)).alias(expr.output_name())
     expr, df = _lower_strings(expr, df)
     name = expr.output_name()
     expr, logical, strict = _prepare(expr, df)
@@ -1638,6 +1827,10 @@ def _gb_lower(df: DataFrame, key: str | tuple | None, aggs: list[Expr], pred: Ex
             exprs.append(x)
             specs.append((base.op, ("input", builtins.len(exprs) - 1)))
             out_logical.append(lg if base.op in ("min", "max", "first", "last", "sum") else None)
+        elif base.kind in ("cum", "lag"):
+            raise N.InvalidOperationError(
+                f"{e!r} is not an aggregation: cum_* / shift / diff give one value per row and are not supported "
+                "inside group_by().agg() on the GPU executor (use .over(keys) in with_columns)")
         else:
             raise N.InvalidOperationError(
                 f"aggregation {e!r} is not supported on the GPU executor "

@@ -67,6 +67,19 @@ _BOOLFUNCS: dict[str, Callable[[Expr], Expr]] = {
 }
 
 
+_CUM_LAG_FUNCS = frozenset({"cum_sum", "cum_min", "cum_max", "cum_count", "cum_prod", "shift", "shift_and_fill",
+                            "diff", "pct_change"})
+
+
+_CUM_LAG_REFUSED = {
+    "cum_sum": ("String", "Date", "Datetime", "Time"),
+    "cum_min": ("String", "Boolean", "Time"),
+    "cum_max": ("String", "Boolean", "Time"),
+    "shift": ("String", "Boolean", "Time"),
+    "diff": ("String", "Boolean", "Date", "Time"),
+}
+
+
 def _dtype_kind(dt) -> str:
     """Name of a polars DataType as the visitor hands it over
     (`Int64`, `Datetime(time_unit='ns', time_zone=None)`, `Enum(categories=...)`)."""
@@ -186,10 +199,56 @@ class _Translator:
                     return self.expr(e.input[0]).is_in(vals, nulls_equal=nulls_equal)
                 except N.InvalidOperationError as exc:
                     raise Unsupported(str(exc)) from exc
+            if fname in _CUM_LAG_FUNCS:
+                return self.cum_lag(e, fd, fname)
             raise Unsupported(f"function {fname}")
         if k == "Window":
             return self.window(e)
         raise Unsupported(f"expression {k}")
+
+    def _literal(self, node: int, what: str):
+        x = self.view(node)
+        if _name(x) != "Literal":
+            raise Unsupported(f"{what} is computed ({_name(x)}): only a literal is taken")
+        return x.value
+
+    def cum_lag(self, e, fd, fname: str) -> Expr:
+        """FunctionExpr::CumSum / CumMin / CumMax / CumCount (function_data
+        (name, reverse), expr_nodes.rs:1265-1269), Shift / ShiftAndFill with
+        inputs [x, n] / [x, n, fill] (:1223-1224) and Diff (("diff",
+        null_behavior), inputs [x, n], :1280) -> Expr.cum_* / shift / diff."""
+        if fname in ("cum_prod", "pct_change"):
+            raise Unsupported(f"function {fname} (not built on the GPU executor)")
+        if self._schema is None:
+            # the mirror evaluates these in select / with_columns only, never
+            # below an aggregation or in a filter predicate
+            raise Unsupported(f"function {fname} outside the expressions of a select / with_columns")
+        kind = self.expr_kind(e.input[0], self._schema)
+        # every input dtype the Series layer refuses (frame.Series._cum / _lag) is gated here, from the scan
+        # schema, so such a query stays on polars instead of failing at collect time
+        base = "shift" if fname == "shift_and_fill" else fname
+        if kind in _CUM_LAG_REFUSED.get(base, ()):
+            raise Unsupported(f"{fname} of a {kind} input")
+        held, self._schema = self._schema, None  # (no window in the function's own input)
+        try:
+            x = self.expr(e.input[0])
+        finally:
+            self._schema = held
+        try:
+            if fname.startswith("cum_"):
+                if len(fd) > 1 and fd[1]:
+                    raise Unsupported(f"{fname} with reverse=True")
+                return getattr(x, fname)()
+            if fname == "diff":
+                behavior = _enum_name(fd[1]).lower() if len(fd) > 1 else "ignore"
+                if behavior != "ignore":
+                    raise Unsupported("diff with null_behavior drop (it changes the length)")
+                return x.diff(self._literal(e.input[1], "diff's n"))
+            n = self._literal(e.input[1], "shift's n")
+            fill = self._literal(e.input[2], "shift's fill_value") if fname == "shift_and_fill" else None
+            return x.shift(n, fill_value=fill)
+        except N.PolaroidError as exc:
+            raise Unsupported(str(exc)) from exc
 
     def window(self, e) -> Expr:
         """Window (expr_nodes.rs:400): an aggregation the group-by translator
@@ -215,9 +274,17 @@ class _Translator:
             keys.append(str(kx.name))
         if not 1 <= len(keys) <= 8:
             raise Unsupported("window partitioned by more than 8 columns")
-        if _name(self.view(e.function)) not in ("Agg", "Len"):
-            raise Unsupported(f"window function {_name(self.view(e.function))}")
-        f = self.agg(e.function, None, self._schema)
+        fx = self.view(e.function)
+        if _name(fx) == "Function":
+            fd = fx.function_data
+            fname = _enum_name(fd[0]) if isinstance(fd, tuple) and fd else _enum_name(fd)
+            if fname not in _CUM_LAG_FUNCS:
+                raise Unsupported(f"window function {fname}")
+            f = self.cum_lag(fx, fd, fname)
+        elif _name(fx) not in ("Agg", "Len"):
+            raise Unsupported(f"window function {_name(fx)}")
+        else:
+            f = self.agg(e.function, None, self._schema)
         try:
             return f.over(keys)
         except N.PolaroidError as exc:
