@@ -212,6 +212,10 @@ typedef struct plgpu_groupby_info {
     int32_t register_runs;       /* 1: fused kernel with per-lane register runs (sorted keys) */
     int32_t key_pack;            /* key columns packed in the fused kernel's registers (0: a key / code column) */
     int32_t part_layout;         /* partitioned path: partition bits | scatter passes << 8 (0: not partitioned) */
+    int32_t fused_variant;       /* the gb_fast_kernel instantiation the fused path launched (0: it did not
+                                    run, i.e. path 0 or 3): bits 0-2 VAR, 3-4 PACK, 5 NULLS, 6 RUNS, 7 DERIV,
+                                    8-9 LIMBS, 10-12 NACC, 13 PRED, 14 SUMONLY, 15 always 1, 16-19 ROWS */
+    int32_t _reserved;           /* 0 (keeps the size a multiple of 8 without implicit padding) */
 } plgpu_groupby_info;
 
 /* ---------------------------------------------------------------- basics */
@@ -667,8 +671,10 @@ int plgpu_str_decode_short(const plgpu_column* codes, plgpu_column* out, void* s
  * (polars-ops/src/frame/join/general.rs:52 _coalesce_full_join). */
 int plgpu_coalesce(const plgpu_column* a, const plgpu_column* b, plgpu_column* out, void* stream);
 
-/* Inner equi-join on one integer key (I64 / I32 / U32; the two sides may
- * differ, values compare as integers).  Produces the matching row pairs as
+/* Inner equi-join on one integer key column per side, both of one dtype
+ * (PLGPU_ERR_SCHEMA "datatypes of join keys don't match" otherwise, as the
+ * reference and plgpu_join_multi; plgpu_join and plgpu_join_inner_take
+ * alike).  Produces the matching row pairs as
  * two UInt32 index columns (the reference's IdxSize pairs).  Null keys match
  * only when nulls_equal != 0.  Replaces
  * polars-ops/src/frame/join/hash_join/single_keys_inner.rs:45

@@ -3064,6 +3064,7 @@ static void gb_fill_info(const GbRun& R, plgpu_groupby_info* info) {
     info->register_runs = p.n_full > 0 && !R.part && R.pl.launched_runs ? 1 : 0;
     info->key_pack = p.kp.n;
     info->part_layout = R.part ? (R.pbits | (R.part_levels << 8)) : 0;
+    info->fused_variant = p.n_full > 0 && !R.part ? R.pl.launched_variant : 0;
     for (int a = 0; a < p.nacc; ++a)
         if (((R.st[ST_FXFLAGS] >> (2 * a)) & 2u) && !((R.wide >> a) & 1u)) info->sum_inexact |= 1 << a;
 }

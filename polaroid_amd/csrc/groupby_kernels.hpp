@@ -220,8 +220,8 @@ enum : uint32_t {
     CK_PART_POS = 128,    // partition scatter position outside the buffers
     CK_KEY_ROW = 256,     // multi-key output key row outside [0, n)
     CK_PERM = 512,        // group-order permutation entry outside [0, groups)
-    CK_REGION = 1024,     // compact region slot outside its partition's region / the region table
-    CK_FIELD = 1024       // apply_row: table field outside [0, nfields)
+    CK_FIELD = 1024,      // apply_row: table field outside [0, nfields)
+    CK_REGION = 2048      // compact region slot outside its partition's region / the region table
 };
 #ifdef PLGPU_CHECKS
 // one copy per translation unit (the fused kernels are compiled in
@@ -1912,23 +1912,25 @@ struct OutSpec {
 };
 
 struct Plan {
-    GbParams p;
+    GbParams p = {};
     std::vector<OutSpec> outs;
-    int acc_of_agg[64];
-    int acc_in[kMaxAcc];  // the input index each acc aggregates
-    size_t lds_bytes;
-    int grid;
-    bool use_lds;
+    int acc_of_agg[64] = {};
+    int acc_in[kMaxAcc] = {};  // the input index each acc aggregates
+    size_t lds_bytes = 0;
+    int grid = 0;
+    bool use_lds = false;
     bool sum_only = false;
     int limbs = 3;     // SUMONLY: 40-bit LDS limbs per f64 sum (3, or 2 for narrow exponent spans)
-    int fast_grid;
-    bool runs;         // sampled keys mostly equal their next row's (sorted / clustered input)
-    bool local;        // range-local mode: contiguous tiles per workgroup, LDS sized by range-local keys
+    int fast_grid = 0;
+    bool runs = false; // sampled keys mostly equal their next row's (sorted / clustered input)
+    bool local = false;  // range-local mode: contiguous tiles per workgroup, LDS sized by range-local keys
     bool part_racc = false;  // partitioned path: register accumulators (clustered / sorted keys)
     bool nulls = false;      // the fused kernel's NULLS variant (nullable key / values / predicate)
-    mutable int launched_grid;  // grid of the last fast launch (info)
+    mutable int launched_grid = 0;  // grid of the last fast launch (info)
     mutable bool launched_runs = false;  // that launch used the register-run variant (info)
     mutable bool launched_var = false;   // that launch was the variance-triple variant (info)
+    // that launch's gb_fast_kernel template arguments (plgpu_groupby_info.fused_variant's layout; 0: none yet)
+    mutable int32_t launched_variant = 0;
 };
 
 // Workgroups of `kern` resident per CU at this LDS size (cached).
@@ -1998,6 +2000,9 @@ hipError_t launch_fast_rows(const Plan& pl, const DevProgram& dp, hipStream_t s)
     pl.launched_grid = grid;
     pl.launched_runs = RUNS;
     pl.launched_var = VAR == 1 || VAR == 4;
+    static_assert(VAR < 8 && PACK < 4 && LIMBS < 4 && NACC < 8 && PRED < 2 && ROWS < 16, "fused_variant's fields");
+    pl.launched_variant = VAR | PACK << 3 | (NULLS ? 1 : 0) << 5 | (RUNS ? 1 : 0) << 6 | (DERIV ? 1 : 0) << 7 |
+                          LIMBS << 8 | NACC << 10 | PRED << 13 | (SUMONLY ? 1 : 0) << 14 | 1 << 15 | ROWS << 16;
     if (pl.local) {
         const int64_t tile = (int64_t)kGbThreads * ROWS;
         const int64_t nall = q.n_full / tile + (pl.p.n > q.n_full ? 1 : 0);

@@ -1435,6 +1435,15 @@ static int check_key(const plgpu_column* k) {
     return PLGPU_OK;
 }
 
+// Both keys, and that they have one dtype (the kernels read the two columns
+// with one element type; plgpu_join_multi checks the same per key).
+static int check_keys(const plgpu_column* l, const plgpu_column* r) {
+    int rc;
+    if ((rc = check_key(l)) || (rc = check_key(r))) return rc;
+    if (l->dtype != r->dtype) return fail(PLGPU_ERR_SCHEMA, "datatypes of join keys don't match");
+    return PLGPU_OK;
+}
+
 // Stable sort of the pairs by the left (or right) index, a null index last.
 static int jn_sort_pairs(plgpu_column* li, plgpu_column* ri, bool by_right, hipStream_t s) {
     plgpu_column perm;
@@ -1666,7 +1675,7 @@ PLGPU_API int plgpu_join(const plgpu_column* left_key, const plgpu_column* right
                          int32_t maintain_order, int32_t validate, plgpu_column* out_left_idx,
                          plgpu_column* out_right_idx, void* stream) {
     int rc;
-    if ((rc = check_key(left_key)) || (rc = check_key(right_key))) return rc;
+    if ((rc = check_keys(left_key, right_key))) return rc;
     if (out_left_idx == nullptr || out_right_idx == nullptr) return fail(PLGPU_ERR_INVALID, "NULL output");
     if ((rc = check_args(how, maintain_order, validate))) return rc;
     return join_impl(left_key, right_key, how, nulls_equal != 0, maintain_order, validate, out_left_idx,
@@ -2128,8 +2137,7 @@ PLGPU_API int plgpu_join_inner_take(const plgpu_column* left_key, const plgpu_co
     for (int i = 0; i < nleft; ++i) std::memset(&out_left[i], 0, sizeof out_left[i]);
     for (int i = 0; i < nright; ++i) std::memset(&out_right[i], 0, sizeof out_right[i]);
     *out_len = 0;
-    int rc = check_key(left_key);
-    if (!rc) rc = check_key(right_key);
+    int rc = check_keys(left_key, right_key);
     if (!rc) rc = check_args(PLGPU_JOIN_INNER, maintain_order, validate);
     for (int i = 0; i < nleft && !rc; ++i)
         if (left_cols[i].length != left_key->length) rc = fail(PLGPU_ERR_SHAPE, "left column length differs");

@@ -24,6 +24,7 @@ import pyarrow as pa
 import pytest
 
 import polaroid_amd as pl
+from polaroid_amd._native import fused_variant
 from conftest import load_golden
 from oracle import oracle as O
 from test_gpu_groupby_multi import _check
@@ -187,9 +188,13 @@ def test_categorical_golden(gpu):
 @pytest.mark.parametrize("nulls", [False, True])
 @pytest.mark.parametrize("maintain_order", [False, True])
 def test_categorical_headline_vs_strings(gpu, nulls, maintain_order):
-    """The headline query on a Categorical symbol: grouped by the codes
-    (fused 4-byte key when null-free) and identical to the same query on the
-    String column."""
+    """The headline query (four sums under close > 250, the predicate's
+    column last, and len) on a Categorical symbol: grouped by the codes,
+    bit-equal to the oracle's group-by on the same UInt32 codes and identical
+    to the same query on the String column.  Null-free, the fused kernel
+    packs the 4-byte key (PACK 1) and, on the sum-only layout, runs the
+    unsigned-limb variant (VAR 5); maintain_order adds the first-row field,
+    so the mixed layout runs and VAR 5 (sum-only) cannot."""
     rng = np.random.default_rng(int(nulls) * 2 + maintain_order)
     syms = np.array([f"SYM{i:03d}" for i in range(100)], dtype=object)
     k = rng.integers(0, 100, N)
@@ -197,25 +202,59 @@ def test_categorical_headline_vs_strings(gpu, nulls, maintain_order):
     if nulls:
         for i in rng.integers(0, N, 1000):
             strs[i] = None
-    close = rng.uniform(10, 490, N)
-    df = _cat_frame(strs, close)
+    names = ["open", "high", "low", "close"]
+    vals = {c: rng.uniform(10, 490, N) for c in names}
+    vser = [pl.Series.from_numpy(c, v) for c, v in vals.items()]
+    arr = pa.array(strs, pa.string()).dictionary_encode()
+    df = pl.DataFrame([pl.Series.from_arrow("c", arr)] + vser)
     info = {}
-    q = df.lazy().filter(pl.col("v") > 250.0).group_by("c", maintain_order=maintain_order).agg(
-        pl.col("v").sum().alias("s"), pl.len())
-    out = q.collect(info=info)
+
+    def query(frame):
+        return frame.lazy().filter(pl.col("close") > 250.0).group_by("c", maintain_order=maintain_order).agg(
+            *[pl.col(c).sum() for c in names], pl.len())
+
+    out = query(df).collect(info=info)
+    fv = fused_variant(info)
     assert info["categorical_codes"] == 1
     assert info["key_pack"] == (0 if nulls else 1), info
-    sdf = pl.DataFrame([pl.Series("c", strs, pl.String), pl.Series.from_numpy("v", close)])
-    ref = sdf.lazy().filter(pl.col("v") > 250.0).group_by("c", maintain_order=maintain_order).agg(
-        pl.col("v").sum().alias("s"), pl.len()).collect()
-    a = sorted(zip(out["c"].to_list(), out["s"].to_list(), out["len"].to_list()), key=str)
-    b = sorted(zip(ref["c"].to_list(), ref["s"].to_list(), ref["len"].to_list()), key=str)
+    if not nulls:
+        assert fv["pack"] == 1 and fv["nacc"] == 4 and fv["pred"] == 1, (info, fv)
+        if maintain_order:
+            assert not fv["sumonly"] and fv["var"] == 0, (info, fv)
+        else:
+            assert info["path"] == 2 and fv["var"] == 5 and fv["limbs"] == 2, (info, fv)
+    # the oracle on the codes (a null code: the null group)
+    kvalid = ~np.asarray(arr.indices.is_null())
+    codes = np.asarray(arr.indices.fill_null(0)).astype(np.uint32)
+    pool = arr.dictionary.to_pylist()
+    hc = [O.HostCol(vals[c]) for c in ["close", "open", "high", "low"]]
+    okeys, oouts = O.group_by_agg_multi([(codes, kvalid if nulls else None)], hc,
+                                        [(1, 0, 0), (2, 0, 250.0), (24, 0, 0)],
+                                        [("sum", 1), ("sum", 2), ("sum", 3), ("sum", 0), ("len", 0)], N)
+    (ok, okv), = okeys
+    okl = [pool[int(c)] if v else None for c, v in zip(ok, okv)]
+    want = {key: ([o[0][i] for o in oouts[:4]], int(oouts[4][0][i])) for i, key in enumerate(okl)}
+    gkeys = out["c"].to_list()
+    assert len(gkeys) == len(want) and set(gkeys) == set(want)
+    vc = [out[c].to_numpy() for c in names]
+    lens = out["len"].to_list()
+    for i, key in enumerate(gkeys):
+        got = np.array([v[i] for v in vc])
+        assert np.array_equal(got.view(np.int64), np.array(want[key][0]).view(np.int64)), key
+        assert lens[i] == want[key][1], key
+    if maintain_order:
+        assert gkeys == okl  # first-occurrence order of the selected rows
+    sdf = pl.DataFrame([pl.Series("c", strs, pl.String)] + vser)
+    ref = query(sdf).collect()
+    cols_ = ["c"] + names + ["len"]
+    a = sorted(zip(*[out[c].to_list() for c in cols_]), key=str)
+    b = sorted(zip(*[ref[c].to_list() for c in cols_]), key=str)
     assert a == b
     if maintain_order:
         assert out["c"].to_list() == ref["c"].to_list()
     # the output keys stay codes over the dictionary until exported
-    arr = out["c"].to_arrow()
-    assert pa.types.is_dictionary(arr.type) and arr.to_pylist() == out["c"].to_list()
+    oarr = out["c"].to_arrow()
+    assert pa.types.is_dictionary(oarr.type) and oarr.to_pylist() == out["c"].to_list()
 
 
 def test_categorical_key_also_used_elsewhere(gpu):
@@ -288,57 +327,178 @@ _NONNEG_PREDS = {  # name -> (expr, the oracle's program over column 0 = close)
 }
 
 
+_NONNEG_N = {"int64": 400_003, "runs": 400_003, "int64_nulls": 400_003}  # the others: _PACKED_N
+_PACKED_N = 2**20 + 515  # just over the fused packing threshold (2^20 rows), no multiple of any tile
+_NONNEG_PACK = {"int64": 0, "runs": 0, "int64_nulls": 0, "sym_day": 1, "i32": 1, "cat": 1, "str": 2}
+_NONNEG_KEY_PACK = {"int64": 0, "runs": 0, "int64_nulls": 0, "sym_day": 2, "i32": 1, "cat": 1, "str": 1}
+_HOT = 0.65         # share of the rows in the hot group (see _nonneg_data)
+_SUBNORMAL = 5e-324
+
+
+def _nonneg_data(pname, keys, order):
+    """Inputs of test_nonneg_predicate_column_sum: (n, key arrays for the
+    oracle, key pool or None, value columns, validity, names)."""
+    rng = np.random.default_rng(len(pname) + 7 * len(keys) + len(order))
+    n = _NONNEG_N.get(keys, _PACKED_N)
+    names = ["open", "high", "low", "close"] if order == "close_last" else ["close", "open", "high", "low"]
+    # magnitudes in [1, 500) with either sign: nine binades, so that every
+    # selected nonzero value fits the 2-limb window (19 binades below the
+    # largest sampled exponent); values nearer zero would send the plan to
+    # three limbs (correctly), where VAR 5 does not exist
+    cols = {c: rng.uniform(1, 500, n) * rng.choice([-1.0, 1.0], n) for c in names}
+    x = cols["close"]
+    x[rng.random(n) < 0.05] = 0.0
+    x[rng.random(n) < 0.05] = -0.0
+    x[rng.random(n) < 0.02] = 3.5
+    x[rng.integers(0, n, 30)] = np.nan
+    x[rng.integers(0, n, 20)] = np.inf
+    x[rng.integers(0, n, 20)] = -np.inf
+    x[rng.integers(0, n, 200)] = np.nextafter(250.0, 0)
+    x[rng.integers(0, n, 200)] = np.nextafter(250.0, 500)
+    if pname in ("gt250", "eq0", "eq"):
+        # the smallest subnormal, where the predicate rejects it (it is
+        # neither == 0 nor > 250).  A selected one lies below every 2-limb
+        # window, so the call reruns with three limbs:
+        # test_nonneg_selected_subnormal_takes_three_limbs.  The rows avoid
+        # the plan's samples (16-row clusters every n // 4096 rows): under
+        # eq0 no selected nonzero close is sampled, the plan samples the
+        # columns unfiltered, and a sampled subnormal chooses three limbs.
+        r = rng.integers(0, n - 64, 40)
+        x[np.where(r % (n // 4096) < 16, r + 16, r)] = _SUBNORMAL
+    # one hot group, its close in [499, 500): the unsigned limbs of one slot
+    # carry as often as this size allows.  65 % of the rows, not more: above
+    # ~70 % most sampled rows equal their successor's key and the plan takes
+    # the register-run kernel (RUNS) for every layout, which has no VAR 5.
+    hot = rng.random(n) < _HOT
+    x[hot] = rng.uniform(499.0, 500.0, int(hot.sum()))
+    x[rng.choice(n, 2000, replace=False)] = 250.0
+    sym = rng.integers(0, 100, n).astype(np.int64)
+    sym[hot] = 37
+    pool = None
+    if keys == "runs":
+        sym = np.sort(sym)
+    if keys == "sym_day":
+        day = ((np.arange(n) * 4) // n).astype(np.int32)  # 100 x 4 tuples: one 1,024-slot LDS table
+        day[hot] = 2
+        hk = [sym * 7919 + 1_000_000, day]
+    elif keys == "i32":
+        k = (sym * 1_000_003 - (1 << 30)).astype(np.int32)
+        for v in (np.iinfo(np.int32).min, -1, np.iinfo(np.int32).max):
+            k[rng.integers(0, n, 50)] = v
+        hk = [k]
+    elif keys in ("cat", "str"):
+        # at most 7 bytes, "" included (the String key's exact short codes)
+        pool = np.array([f"SYM{i:03d}" for i in range(98)] + ["", "abcdefg"], dtype=object)
+        hk = [sym]
+    else:
+        hk = [sym]
+    valid = {c: (rng.random(n) > 0.02 if keys == "int64_nulls" else None) for c in names}
+    return n, hk, pool, cols, valid, names
+
+
+def _nonneg_frame(keys, hk, pool, cols, valid):
+    vals = [pl.Series.from_numpy(c, v, valid[c]) for c, v in cols.items()]
+    if keys == "cat":
+        return pl.DataFrame([_cat_frame(pool[hk[0]].tolist())["c"]] + vals), ["c"]
+    if keys == "str":
+        return pl.DataFrame([pl.Series("s", pool[hk[0]].tolist(), pl.String)] + vals), ["s"]
+    by = ["sym", "day"][:len(hk)]
+    return pl.DataFrame([pl.Series.from_numpy(nm, k) for nm, k in zip(by, hk)] + vals), by
+
+
 @pytest.mark.parametrize("pname", list(_NONNEG_PREDS))
-@pytest.mark.parametrize("keys", ["int64", "sym_day", "runs", "int64_nulls"])
+@pytest.mark.parametrize("keys", ["int64", "sym_day", "runs", "int64_nulls", "i32", "cat", "str"])
 @pytest.mark.parametrize("order", ["close_last", "close_first"])
 def test_nonneg_predicate_column_sum(gpu, plgpu_option, pname, keys, order):
     """Four sums whose last column is the fused predicate's and keeps no
     value below a literal >= 0 (the headline's close.sum() under
     close > 250) run the variant whose last limbs carry no sign
     (gb_fast_kernel VAR 5, option sum_pos).  Checked bit-exact against the
-    oracle (or_group_by_agg, SUM_EXACT) with the option on and off, on data
-    with negatives, zeros, -0.0, NaN, +inf and exact hits of the literal;
-    keys: an Int64 key, (Int64, Int32) packed in the kernel, and a sorted
-    key (the RUNS layout), and an Int64 key over value columns with ~2 %
-    nulls (the NULLS variant; a null close drops its row, so VAR 5 still
-    holds).  close_first puts the predicate's column in the
-    first acc: var_x_nonneg's pred_acc is then 0 and the signed kernel runs
-    (gtneg: a negative literal, never the unsigned variant)."""
-    rng = np.random.default_rng(len(pname) + len(keys) + len(order))
-    n = 400_003
-    sym = rng.integers(0, 100, n).astype(np.int64)
-    if keys == "runs":
-        sym = np.sort(sym)
-    day = (np.arange(n) // 5000).astype(np.int32)
-    names = ["open", "high", "low", "close"] if order == "close_last" else ["close", "open", "high", "low"]
-    cols = {c: rng.uniform(-500, 500, n) for c in names}
+    oracle (or_group_by_agg, SUM_EXACT) with the option on and off, and the
+    instantiation each call launched is read back (info["fused_variant"]):
+    VAR 5 with the option on, the column last and a literal >= 0; the signed
+    kernel otherwise (close_first: var_x_nonneg's pred_acc is then 0; gtneg:
+    a negative literal; option off), so on / off never compare one kernel
+    with itself.  Data: negatives, zeros, -0.0, NaN, +-inf, exact hits of
+    the literals, the doubles next to 250.0 on both sides, the smallest
+    subnormal, and a hot group of large values (_nonneg_data).
+    Key layouts: an Int64 key; (Int64, Int32), one Int32 key with the type's
+    extremes and -1, and a Categorical's UInt32 codes, all packed in the
+    kernel (PACK 1: the benchmark's Categorical and (symbol, day) legs); a
+    String key of at most 7 bytes (PACK 2); a sorted Int64 key, which takes
+    the register-run kernel (launch_fast tests pl.runs first) and never VAR
+    5; and an Int64 key over value columns with ~2 % nulls (the NULLS
+    variant; a null close drops its row, so VAR 5 still holds)."""
+    n, hk, pool, cols, valid, names = _nonneg_data(pname, keys, order)
     x = cols["close"]
-    x[rng.random(n) < 0.05] = 0.0
-    x[rng.random(n) < 0.05] = -0.0
-    x[rng.random(n) < 0.02] = 3.5
-    x[rng.integers(0, n, 3)] = np.nan
-    x[rng.integers(0, n, 2)] = np.inf
-    x[rng.integers(0, n, 2)] = -np.inf
-    valid = {c: (rng.random(n) > 0.02 if keys == "int64_nulls" else None) for c in names}
-    df = pl.DataFrame({"sym": pl.Series.from_numpy("sym", sym), "day": pl.Series.from_numpy("day", day),
-                       **{c: pl.Series.from_numpy(c, v, valid[c]) for c, v in cols.items()}})
+    # (the later writes of _nonneg_data overwrite earlier ones: each special survives)
+    assert np.isnan(x).any() and (x == np.inf).any() and (x == -np.inf).any() and (x < 0).any()
+    assert (x == np.nextafter(250.0, 0)).any() and (x == np.nextafter(250.0, 500)).any()
+    assert (x == 250.0).sum() >= 2000 and (x == 3.5).any() and (np.signbit(x) & (x == 0)).any()
+    assert (x == _SUBNORMAL).any() == (pname in ("gt250", "eq0", "eq"))
+    df, by = _nonneg_frame(keys, hk, pool, cols, valid)
     mk, prog = _NONNEG_PREDS[pname]
-    by = ["sym", "day"] if keys == "sym_day" else ["sym"]
-    hk = [(sym, None)] + ([(day, None)] if keys == "sym_day" else [])
-    hc = [O.HostCol(cols[c], valid[c]) for c in ["close"] + [c for c in names if c != "close"]]
-    oidx = {c: i for i, c in enumerate(["close"] + [c for c in names if c != "close"])}
-    okeys, oouts = O.group_by_agg_multi(hk, hc, prog, [("sum", oidx[c]) for c in names], n)
-    want = {tuple(int(k[0][i]) for k in okeys): [o[0][i] for o in oouts] for i in range(len(okeys[0][0]))}
+    onames = ["close"] + [c for c in names if c != "close"]
+    hc = [O.HostCol(cols[c], valid[c]) for c in onames]
+    oidx = {c: i for i, c in enumerate(onames)}
+    okeys, oouts = O.group_by_agg_multi([(k, None) for k in hk], hc, prog, [("sum", oidx[c]) for c in names], n)
+    unkey = (lambda v: pool[int(v)]) if pool is not None else int
+    want = {tuple(unkey(k[0][i]) for k in okeys): [o[0][i] for o in oouts] for i in range(len(okeys[0][0]))}
     for on in (1, 0):
         plgpu_option("sum_pos", on)
         info = {}
         out = df.lazy().filter(mk()).group_by(*by).agg(*[pl.col(c).sum() for c in names]).collect(info=info)
-        assert out.height == len(want), (pname, on)
-        if keys != "sym_day":  # (8,001 (sym, day) groups over 4e5 rows: the plan's choice)
-            assert info["path"] == 2, info
-        kc = [out[k].to_numpy() for k in by]
+        fv = fused_variant(info)
+        tag = (pname, keys, order, on, info, fv)
+        assert out.height == len(want), tag
+        assert info["path"] == 2 and info["sum_limbs"] == 2, tag
+        assert info["key_pack"] == _NONNEG_KEY_PACK[keys], tag
+        assert info.get("categorical_codes", 0) == (1 if keys == "cat" else 0), tag
+        assert fv["pack"] == _NONNEG_PACK[keys] and fv["nulls"] == (keys == "int64_nulls"), tag
+        assert fv["nacc"] == 4 and fv["pred"] == 1 and fv["sumonly"] and fv["limbs"] == 2, tag
+        if keys == "runs":
+            assert fv["runs"] and fv["var"] == 0 and info["register_runs"] == 1, tag
+        elif on == 1 and order == "close_last" and pname != "gtneg":
+            assert fv["var"] == 5 and not fv["runs"], tag
+        else:
+            assert fv["var"] == 0 and not fv["runs"], tag
+        kc = [out[k].to_list() for k in by]
         vc = [out[c].to_numpy() for c in names]
         for i in range(out.height):
-            w = want[tuple(int(k[i]) for k in kc)]
+            w = want[tuple(k[i] for k in kc)]
             got = np.array([v[i] for v in vc])
-            assert np.array_equal(got.view(np.int64), np.array(w).view(np.int64)), (pname, keys, order, on, i)
+            assert np.array_equal(got.view(np.int64), np.array(w).view(np.int64)), (tag, i)
+
+
+@pytest.mark.parametrize("pname", ["gt0", "ge0"])
+def test_nonneg_selected_subnormal_takes_three_limbs(gpu, pname):
+    """A selected subnormal (5e-324 passes > 0 and >= 0) has bits below every
+    2-limb window: the 2-limb pass flags it and the call runs again on three
+    limbs (info["reruns"]), where the unsigned variant does not exist
+    (launch_fast: VAR 5 needs pl.limbs == 2).  Still bit-exact against the
+    oracle."""
+    rng = np.random.default_rng(len(pname))
+    n = 400_003
+    sym = rng.integers(0, 100, n).astype(np.int64)
+    names = ["open", "high", "low", "close"]
+    cols = {c: rng.uniform(1, 500, n) * rng.choice([-1.0, 1.0], n) for c in names}
+    cols["close"][rng.random(n) < 0.05] = -0.0
+    # (off the plan's sampled rows, 16-row clusters every n // 4096 rows: the
+    # plan then chooses two limbs and the main pass has to catch the value)
+    r = rng.integers(0, n - 64, 40)
+    cols["close"][np.where(r % (n // 4096) < 16, r + 16, r)] = _SUBNORMAL
+    df = pl.DataFrame([pl.Series.from_numpy("sym", sym)] + [pl.Series.from_numpy(c, v) for c, v in cols.items()])
+    mk, prog = _NONNEG_PREDS[pname]
+    hc = [O.HostCol(cols[c]) for c in ["close", "open", "high", "low"]]
+    okeys, oouts = O.group_by_agg_multi([(sym, None)], hc, prog, [("sum", i) for i in (1, 2, 3, 0)], n)
+    want = {int(okeys[0][0][i]): [o[0][i] for o in oouts] for i in range(len(okeys[0][0]))}
+    info = {}
+    out = df.lazy().filter(mk()).group_by("sym").agg(*[pl.col(c).sum() for c in names]).collect(info=info)
+    fv = fused_variant(info)
+    assert info["path"] == 2 and info["sum_limbs"] == 3 and info["reruns"] >= 1, (info, fv)
+    assert fv["var"] == 0 and fv["limbs"] == 3 and fv["nacc"] == 4, (info, fv)
+    assert out.height == len(want)
+    vc = [out[c].to_numpy() for c in names]
+    for i, k in enumerate(out["sym"].to_list()):
+        got = np.array([v[i] for v in vc])
+        assert np.array_equal(got.view(np.int64), np.array(want[k]).view(np.int64)), (pname, k)

@@ -155,6 +155,44 @@ def test_radix_join_key_listed_twice_and_absent(gpu, plgpu_option):
                 assert np.array_equal(outs[i].to_numpy()[a], lk[ol[b]])
 
 
+@pytest.mark.parametrize("radix", [0, 2])
+def test_single_key_joins_refuse_mixed_key_dtypes(gpu, plgpu_option, radix):
+    """Through the C-ABI: an Int64 key against a UInt64 key (the same width,
+    so nothing could be read out of bounds) is a SchemaMismatch from
+    plgpu_join_inner_take, plgpu_join_inner and plgpu_join alike, as from
+    plgpu_join_inner_take_multi, and no output column is produced; the radix
+    path forced (2) or off (0)."""
+    from polaroid_amd.frame import _col_array
+
+    plgpu_option("join_radix", radix)
+    plgpu_option("join_radix_keys", 128)
+    nl, nr = 5000, 700
+    rng = np.random.default_rng(radix)
+    rk = rng.permutation(4000)[:nr]
+    sk = pl.Series.from_numpy("k", rk[rng.integers(0, nr, nl)].astype(np.int64))
+    sl = pl.Series.from_numpy("li", np.arange(nl, dtype=np.int64))
+    sr = pl.Series.from_numpy("k", rk.astype(np.uint64))
+    sp = pl.Series.from_numpy("p", np.arange(nr, dtype=np.int64))
+    assert sk._col.dtype == N.I64 and sr._col.dtype != N.I64
+    ol_, or_, nout = (N.Column * 2)(), (N.Column * 1)(), C.c_int64(-1)
+    rc = N.lib().plgpu_join_inner_take(C.byref(sk._col), C.byref(sr._col), _col_array([sk, sl]), 2,
+                                       _col_array([sp]), 1, 0, N.JOIN_ORDER["none"], N.JOIN_VALIDATE["m:m"],
+                                       ol_, or_, C.byref(nout), None)
+    assert rc == N.ERR_SCHEMA, rc
+    assert "datatypes of join keys don't match" in N.lib().plgpu_last_error().decode()
+    assert nout.value == 0
+    for c in (ol_[0], ol_[1], or_[0]):
+        assert not c.values and not c.release and c.length == 0
+    for call in (lambda li, ri: N.lib().plgpu_join_inner(C.byref(sk._col), C.byref(sr._col), 0, N.JOIN_ORDER["none"],
+                                                         N.JOIN_VALIDATE["m:m"], C.byref(li), C.byref(ri), None),
+                 lambda li, ri: N.lib().plgpu_join(C.byref(sk._col), C.byref(sr._col), N.JOIN_HOW["left"], 0,
+                                                   N.JOIN_ORDER["none"], N.JOIN_VALIDATE["m:m"], C.byref(li),
+                                                   C.byref(ri), None)):
+        li, ri = N.Column(), N.Column()
+        assert call(li, ri) == N.ERR_SCHEMA
+        assert not li.values and not li.release and not ri.values and not ri.release
+
+
 @pytest.mark.slow
 def test_radix_join_default_path_sampled_estimate(gpu):
     """Default thresholds (probe >= 2^22 rows, build >= 2^17 keys): the
