@@ -891,6 +891,30 @@ int plgpu_lag(const plgpu_column* values, const plgpu_column* seg_starts, int32_
               int32_t has_fill, int64_t fill_bits /* value bits in the column's dtype */,
               plgpu_column* out, void* stream);
 
+/* ---- forward / backward fill ---------------------------------------------------
+ * plgpu_fill: the nulls of a column replaced by the closest non-null value
+ * before (FORWARD) or after (BACKWARD) them, at a distance of at most `limit`
+ * rows (limit < 0: any distance; 0 fills nothing) and never across a set bit of
+ * seg_starts (NULL: one segment; else a null-free Boolean column of the values'
+ * length, as plgpu_segment_starts writes it).  Replaces
+ * polars-core/src/chunked_array/ops/fill_null.rs:58 Series::fill_null with
+ * FillNullStrategy::Forward / Backward: :130 fill_forward_numeric, :160
+ * fill_backward_numeric, :258 fill_forward_gather_limit, :304
+ * fill_backward_gather_limit, and with seg_starts their evaluation on every
+ * group's rows (polars-expr/src/expressions/window.rs:356, GroupsToRows).  A
+ * non-null row keeps its value; leading (FORWARD) / trailing (BACKWARD) nulls
+ * of a column or segment stay null.  Values are moved as their bits (a NaN
+ * keeps its payload, -0.0 stays -0.0).  4- and 8-byte dtypes; the output keeps
+ * the dtype.  A column without a validity buffer is copied (no kernel runs).
+ * PLGPU_ERR_INVALID: a NULL values / out, an unknown kind, a seg_starts that is
+ * not a null-free Boolean column of the values' length; PLGPU_ERR_SCHEMA: any
+ * other dtype; both before any device work.  n == 0 is legal.
+ * Three launches over the bitmaps and one pass over the values (bitmap reduce
+ * per tile, scan of the tile summaries, apply); no workgroup waits on another. */
+enum plgpu_fill_kind { PLGPU_FILL_FORWARD = 1, PLGPU_FILL_BACKWARD = 2 };
+int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_starts /* NULL: one segment */,
+               int32_t kind, int64_t limit /* < 0: no limit */, plgpu_column* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,7 @@ SIGNATURES = {
     "plgpu_invert_permutation": (C.c_int, [_COLP, _COLP, _P]),
     "plgpu_cumulative": (C.c_int, [_COLP, _COLP, C.c_int32, _COLP, _P]),
     "plgpu_lag": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _COLP, _P]),
+    "plgpu_fill": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, _COLP, _P]),
 }
 
 GB_MAX_ACC = 6
@@ -219,6 +220,7 @@ JOIN_HOW = {"inner": 0, "left": 1, "right": 2, "full": 3, "semi": 4, "anti": 5}
 ROLLING = {"sum": 1, "mean": 2, "min": 3, "max": 4, "var": 5, "std": 6}
 CUM = {"sum": 1, "min": 2, "max": 3, "count": 4}
 LAG = {"shift": 1, "diff": 2}
+FILL = {"forward": 1, "backward": 2}
 CUM_BLOCK = 2048            # kCumBlock (csrc/cumulative.hip): rows of one workgroup scan
 CUM_TILE = 8 * CUM_BLOCK    # kCumTile: rows per workgroup of the scan kernels (one summary / carry each)
 

@@ -1,0 +1,422 @@
+// Forward / backward fill of the nulls of one column, plain or per segment
+// (forward_fill / backward_fill / fill_null(strategy="forward" | "backward")).
+//
+// Reference (paths under the polars crates):
+//   polars-core/src/chunked_array/ops/fill_null.rs:58 Series::fill_null, :130 /
+//   :160 fill_forward_numeric / fill_backward_numeric, :258 / :304
+//   fill_forward_gather_limit / fill_backward_gather_limit; over groups
+//   polars-expr/src/expressions/window.rs:356 with GroupsToRows.
+//
+// MI355X design (DESIGN.md "Fill strategies"): the fill is a scan over bitmaps,
+// and the values are touched once.  For row i the answer is j(i), the last row
+// <= i whose validity bit is set, and s(i), the last row <= i whose
+// segment-start bit is set; the row is filled iff j exists, j >= s(i) and
+// i - j <= limit.  Both are plain running maxima of row indices, so no
+// segmented operator is needed.  Rows are held as codes, 0 for none: row + 1
+// forward; backward kRevTop - row, and the start bitmap is read one bit on (a
+// set bit then marks the last row of a segment), so the closest row in the
+// direction of the scan always has the largest code and both directions run
+// the same maxima and the same test.
+//
+// Three launches, none of which waits on another workgroup:
+// fill_reduce_kernel reads the bitmaps alone, one 64-row word per lane, and
+// leaves two codes per tile of kFillTile rows; fill_totals_kernel (one
+// workgroup) turns them into every tile's carry, an exclusive running maximum
+// in the direction of the fill; fill_apply_kernel scans the per-word codes of
+// its tile, adds the carry, and streams the values once: a null row that
+// passes the test takes x[j] from the lane's own registers when j lies in the
+// lane's rows, else by one load per lane (the line just streamed, or for a
+// long run one address for the whole wave).  Values are moved as their bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+
+#include "plgpu_internal.hpp"
+
+namespace plgpu {
+namespace {
+
+constexpr int kFillThreads = 256;
+constexpr int kFillPer = 8;                          // consecutive rows per thread
+constexpr int kFillBlock = kFillThreads * kFillPer;  // rows of one pass of the workgroup over the values
+constexpr int kFillBlocks = 8;
+constexpr int kFillTile = kFillBlock * kFillBlocks;  // rows per workgroup: kCumTile (cumulative.hip)
+constexpr int kFillWords = kFillTile / 64;           // validity words of a tile: one per thread
+constexpr int kFillTotalsThreads = 1024;
+constexpr uint64_t kRevTop = 1ull << 62;             // backward codes: kRevTop - row
+static_assert(kFillWords == kFillThreads, "one validity word per thread");
+
+struct FillParams {
+    const void* values;      // the slice's first element is values[voff]
+    int64_t voff;
+    const uint8_t* valid;    // validity bitmap; row r is bit valid_off + r
+    int64_t valid_off;
+    int64_t valid_bytes;     // bytes of the bitmap that hold bits of the slice
+    const uint8_t* seg;      // segment starts (nullptr: one segment), row r is bit seg_off + r
+    int64_t seg_off;
+    int64_t seg_bytes;
+    int64_t n;
+    uint64_t limit;          // largest distance filled
+    void* out;
+    uint8_t* out_valid;
+    uint64_t* cj;            // per tile: code of its last valid row, then the carry
+    uint64_t* cs;            // per tile: code of its last start, then the carry
+    int64_t tiles;
+};
+
+// 8-byte word k of a bitmap of nbytes bytes, zero past its end (a caller's
+// bitmap need not be padded, nor 8-byte aligned).
+__device__ __forceinline__ uint64_t fill_bitmap_word(const uint8_t* b, int64_t nbytes, int64_t k) {
+    if (k * 8 >= nbytes) return 0ull;
+    if ((k + 1) * 8 <= nbytes && ((uintptr_t)b & 7u) == 0) return ((const uint64_t*)b)[k];
+    uint64_t v = 0;
+    const int64_t hi = std::min<int64_t>((k + 1) * 8, nbytes);
+    for (int64_t j = k * 8; j < hi; ++j) v |= (uint64_t)b[j] << (8 * (j - k * 8));
+    return v;
+}
+
+// Bits [bit0, bit0 + 64) of the bitmap: a funnel shift of two words.
+__device__ __forceinline__ uint64_t fill_bits64(const uint8_t* b, int64_t nbytes, int64_t bit0) {
+    const int64_t k = bit0 >> 6;
+    const int sh = (int)(bit0 & 63);
+    const uint64_t lo = fill_bitmap_word(b, nbytes, k);
+    if (sh == 0) return lo;
+    const uint64_t hi = fill_bitmap_word(b, nbytes, k + 1);
+    return (lo >> sh) | (hi << (64 - sh));
+}
+
+__device__ __forceinline__ uint64_t fill_lowmask(int64_t c) {
+    return c >= 64 ? ~0ull : (c <= 0 ? 0ull : (1ull << c) - 1ull);
+}
+
+// Validity bits V and segment bits S of rows [64 w, 64 w + 64), zero past the
+// column.  Backward S: bit r set when row r + 1 starts a segment.
+template <bool REV>
+__device__ __forceinline__ void fill_words(const FillParams& p, int64_t w, bool seg, uint64_t& V, uint64_t& S) {
+    const int64_t r0 = w * 64;
+    V = 0ull;
+    S = 0ull;
+    if (r0 >= p.n) return;
+    V = fill_bits64(p.valid, p.valid_bytes, p.valid_off + r0) & fill_lowmask(p.n - r0);
+    if (seg) {
+        if constexpr (REV) S = fill_bits64(p.seg, p.seg_bytes, p.seg_off + r0 + 1) & fill_lowmask(p.n - 1 - r0);
+        else S = fill_bits64(p.seg, p.seg_bytes, p.seg_off + r0) & fill_lowmask(p.n - r0);
+    }
+}
+
+template <bool REV>
+__device__ __forceinline__ uint64_t fill_row_code(int64_t row) {
+    return REV ? kRevTop - (uint64_t)row : (uint64_t)row + 1ull;
+}
+
+// Code of the set bit of m (rows from r0) closest in the direction of the
+// fill: find-last-set forward, find-first-set backward.  0: none.
+template <bool REV>
+__device__ __forceinline__ uint64_t fill_word_code(uint64_t m, int64_t r0) {
+    if (m == 0ull) return 0ull;
+    const int pos = REV ? __ffsll((unsigned long long)m) - 1 : 63 - __clzll((long long)m);
+    return fill_row_code<REV>(r0 + pos);
+}
+
+__device__ __forceinline__ uint64_t fill_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+
+// Exclusive running maximum of (a, b) over the workgroup's threads, in thread
+// order.  wa / wb: one slot per wave.
+__device__ __forceinline__ void fill_block_excl_max(uint64_t& a, uint64_t& b, uint64_t* wa, uint64_t* wb) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint64_t x = a, y = b;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t xu = __shfl_up(x, off, 64), yu = __shfl_up(y, off, 64);
+        if (lane >= off) {
+            x = fill_max(x, xu);
+            y = fill_max(y, yu);
+        }
+    }
+    if (lane == 63) {
+        wa[wid] = x;
+        wb[wid] = y;
+    }
+    uint64_t px = __shfl_up(x, 1, 64), py = __shfl_up(y, 1, 64);
+    if (lane == 0) {
+        px = 0ull;
+        py = 0ull;
+    }
+    __syncthreads();
+    for (int w = 0; w < wid; ++w) {
+        px = fill_max(px, wa[w]);
+        py = fill_max(py, wb[w]);
+    }
+    __syncthreads();
+    a = px;
+    b = py;
+}
+
+template <bool REV>
+__global__ __launch_bounds__(kFillThreads) void fill_reduce_kernel(FillParams p) {
+    __shared__ uint64_t wa[kFillThreads / 64], wb[kFillThreads / 64];
+    const int64_t tile = blockIdx.x;
+    const int64_t w = tile * kFillWords + threadIdx.x;
+    uint64_t V, S;
+    fill_words<REV>(p, w, p.seg != nullptr, V, S);
+    uint64_t a = fill_word_code<REV>(V, w * 64), b = fill_word_code<REV>(S, w * 64);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a = fill_max(a, __shfl_xor(a, off, 64));
+        b = fill_max(b, __shfl_xor(b, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wa[threadIdx.x >> 6] = a;
+        wb[threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kFillThreads / 64; ++k) {
+            a = fill_max(a, wa[k]);
+            b = fill_max(b, wb[k]);
+        }
+        p.cj[tile] = a;
+        p.cs[tile] = b;
+    }
+}
+
+template <bool REV>
+__global__ __launch_bounds__(kFillTotalsThreads) void fill_totals_kernel(FillParams p) {
+    __shared__ uint64_t wa[kFillTotalsThreads / 64], wb[kFillTotalsThreads / 64];
+    // position q of the scan is tile q forward, tile tiles - 1 - q backward
+    const int64_t per = (p.tiles + kFillTotalsThreads - 1) / kFillTotalsThreads;
+    const int64_t lo = std::min<int64_t>((int64_t)threadIdx.x * per, p.tiles);
+    const int64_t hi = std::min<int64_t>(lo + per, p.tiles);
+    uint64_t a = 0ull, b = 0ull;
+    for (int64_t q = lo; q < hi; ++q) {
+        const int64_t t = REV ? p.tiles - 1 - q : q;
+        a = fill_max(a, p.cj[t]);
+        b = fill_max(b, p.cs[t]);
+    }
+    fill_block_excl_max(a, b, wa, wb);
+    // the carry of a tile: the maximum of the tiles before it in scan order
+    for (int64_t q = lo; q < hi; ++q) {
+        const int64_t t = REV ? p.tiles - 1 - q : q;
+        const uint64_t va = p.cj[t], vb = p.cs[t];
+        p.cj[t] = a;
+        p.cs[t] = b;
+        a = fill_max(a, va);
+        b = fill_max(b, vb);
+    }
+}
+
+template <int BYTES, bool REV, bool SEG>
+__global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) {
+    using T = typename std::conditional<BYTES == 8, uint64_t, uint32_t>::type;
+    __shared__ uint64_t sV[kFillWords], sS[kFillWords], sJ[kFillWords], sT[kFillWords];
+    __shared__ uint64_t wa[kFillThreads / 64], wb[kFillThreads / 64];
+    const int64_t tile = blockIdx.x;
+    const int t = threadIdx.x;
+    {
+        // the codes that enter every word of the tile: thread order is scan order
+        const int wi = REV ? kFillWords - 1 - t : t;
+        const int64_t w = tile * kFillWords + wi;
+        uint64_t V, S;
+        fill_words<REV>(p, w, SEG, V, S);
+        uint64_t a = fill_word_code<REV>(V, w * 64), b = SEG ? fill_word_code<REV>(S, w * 64) : 0ull;
+        fill_block_excl_max(a, b, wa, wb);
+        sV[wi] = V;
+        sS[wi] = S;
+        sJ[wi] = fill_max(a, p.cj[tile]);
+        sT[wi] = SEG ? fill_max(b, p.cs[tile]) : 0ull;
+    }
+    __syncthreads();
+    const T* src = (const T*)p.values + p.voff;
+    T* dst = (T*)p.out;
+    const bool aligned = ((uintptr_t)src & 15u) == 0;
+    const int64_t padded = (p.n + 63) / 64 * 64;
+    for (int blk = 0; blk < kFillBlocks; ++blk) {
+        const int64_t first = tile * kFillTile + (int64_t)blk * kFillBlock;
+        if (first >= p.n) break;
+        const int64_t base = first + (int64_t)t * kFillPer;
+        if (base >= p.n) {  // the rest of the last validity word
+            if (base < padded) p.out_valid[base >> 3] = 0;
+            continue;
+        }
+        const int wi = blk * (kFillBlock / 64) + (t >> 3);
+        const int b0 = (t & 7) * kFillPer;  // the thread's rows are bits b0 .. b0 + 7 of the word
+        const uint64_t V = sV[wi], S = SEG ? sS[wi] : 0ull;
+        const uint32_t vb = (uint32_t)(V >> b0) & 0xFFu, sb = (uint32_t)(S >> b0) & 0xFFu;
+        (void)sb;
+        const bool full = base + kFillPer <= p.n;
+        T x[kFillPer];
+        if (full && aligned) {
+            if constexpr (BYTES == 8) {
+                const ulonglong2* s2 = (const ulonglong2*)(src + base);
+#pragma unroll
+                for (int k = 0; k < kFillPer / 2; ++k) {
+                    const ulonglong2 q = s2[k];
+                    x[2 * k] = q.x;
+                    x[2 * k + 1] = q.y;
+                }
+            } else {
+                const uint4* s4 = (const uint4*)(src + base);
+                const uint4 q0 = s4[0], q1 = s4[1];
+                x[0] = q0.x; x[1] = q0.y; x[2] = q0.z; x[3] = q0.w;
+                x[4] = q1.x; x[5] = q1.y; x[6] = q1.z; x[7] = q1.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kFillPer; ++k) x[k] = base + k < p.n ? src[base + k] : (T)0;
+        }
+        uint32_t ob = vb;
+        if (vb != 0xFFu) {
+            // the codes that enter the thread's rows: the word's bits before
+            // them in scan order, else the word's own entry codes
+            uint64_t mj, ms;
+            if constexpr (REV) {
+                const uint64_t after = b0 + kFillPer == 64 ? 0ull : ~0ull << (b0 + kFillPer);
+                mj = V & after;
+                ms = S & after;
+            } else {
+                const uint64_t before = (1ull << b0) - 1ull;
+                mj = V & before;
+                ms = S & before;
+            }
+            const int64_t r0 = (tile * kFillWords + wi) * 64;
+            uint64_t jc = mj ? fill_word_code<REV>(mj, r0) : sJ[wi];
+            uint64_t sc = 0ull;
+            if constexpr (SEG) sc = ms ? fill_word_code<REV>(ms, r0) : sT[wi];
+            T val = (T)0;
+            bool have = false;  // val holds x[j] of the row code jc
+#pragma unroll
+            for (int kk = 0; kk < kFillPer; ++kk) {
+                const int k = REV ? kFillPer - 1 - kk : kk;
+                const int64_t i = base + k;
+                const uint64_t ic = fill_row_code<REV>(i);
+                if constexpr (SEG) {
+                    if ((sb >> k) & 1u) sc = ic;
+                }
+                if ((vb >> k) & 1u) {
+                    jc = ic;
+                    val = x[k];
+                    have = true;
+                } else if (i < p.n && jc != 0ull && jc >= sc && ic - jc <= p.limit) {
+                    if (!have) {
+                        const int64_t j = REV ? (int64_t)(kRevTop - jc) : (int64_t)(jc - 1ull);
+                        val = src[j];
+                        have = true;
+                    }
+                    x[k] = val;
+                    ob |= 1u << k;
+                }
+            }
+        }
+        if (full) {  // an owned buffer, base a multiple of 8: 16-byte aligned
+            if constexpr (BYTES == 8) {
+                ulonglong2* d2 = (ulonglong2*)(dst + base);
+#pragma unroll
+                for (int k = 0; k < kFillPer / 2; ++k) d2[k] = make_ulonglong2(x[2 * k], x[2 * k + 1]);
+            } else {
+                uint4* d4 = (uint4*)(dst + base);
+                d4[0] = make_uint4(x[0], x[1], x[2], x[3]);
+                d4[1] = make_uint4(x[4], x[5], x[6], x[7]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kFillPer; ++k)
+                if (base + k < p.n) dst[base + k] = x[k];
+        }
+        p.out_valid[base >> 3] = (uint8_t)ob;  // rows past the column: zero bits
+    }
+}
+
+template <int BYTES, bool REV>
+void fill_launch(const FillParams& p, hipStream_t s) {
+    const unsigned g = (unsigned)p.tiles;
+    {
+        KtScope kt("fill_reduce_kernel", s);
+        fill_reduce_kernel<REV><<<g, kFillThreads, 0, s>>>(p);
+    }
+    {
+        KtScope kt("fill_totals_kernel", s);
+        fill_totals_kernel<REV><<<1, kFillTotalsThreads, 0, s>>>(p);
+    }
+    {
+        KtScope kt("fill_apply_kernel", s);
+        if (p.seg) fill_apply_kernel<BYTES, REV, true><<<g, kFillThreads, 0, s>>>(p);
+        else fill_apply_kernel<BYTES, REV, false><<<g, kFillThreads, 0, s>>>(p);
+    }
+}
+
+}  // namespace
+}  // namespace plgpu
+
+using namespace plgpu;
+
+PLGPU_API int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind, int64_t limit,
+                         plgpu_column* out, void* stream) {
+    hipStream_t s = as_stream(stream);
+    if (values == nullptr || out == nullptr) return fail(PLGPU_ERR_INVALID, "NULL argument");
+    std::memset(out, 0, sizeof *out);
+    if (kind != PLGPU_FILL_FORWARD && kind != PLGPU_FILL_BACKWARD) return fail(PLGPU_ERR_INVALID, "unknown fill kind");
+    if (seg_starts != nullptr) {
+        if (seg_starts->dtype != PLGPU_BOOL || seg_starts->validity != nullptr)
+            return fail(PLGPU_ERR_INVALID, "segment starts must be a null-free Boolean column");
+        if (seg_starts->length != values->length)
+            return fail(PLGPU_ERR_INVALID, "segment starts and values must have equal lengths");
+    }
+    const int eb = dtype_bytes(values->dtype);
+    if (eb != 4 && eb != 8)
+        return fail(PLGPU_ERR_SCHEMA, "forward / backward fill input must be a 4- or 8-byte numeric column");
+    const int64_t n = values->length;
+    const bool nullable = values->validity != nullptr;
+    int rc = make_owned_column(out, values->dtype, n, nullable, s);
+    if (rc || n == 0) return rc;
+    hipError_t e = hipSuccess;
+    if (!nullable) {
+        // nothing to fill (the reference returns a clone at null_count == 0): the values, no launch
+        e = hipMemcpyAsync((void*)out->values, (const uint8_t*)values->values + (size_t)values->offset * eb,
+                           (size_t)n * eb, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            plgpu_column_release(out);
+            return hip_fail(e, "fill");
+        }
+        return PLGPU_OK;
+    }
+    FillParams p;
+    std::memset(&p, 0, sizeof p);
+    p.values = values->values;
+    p.voff = values->offset;
+    p.valid = values->validity;
+    p.valid_off = values->offset;
+    p.valid_bytes = (values->offset + n + 7) / 8;
+    if (seg_starts != nullptr) {
+        p.seg = (const uint8_t*)seg_starts->values;
+        p.seg_off = seg_starts->offset;
+        p.seg_bytes = (seg_starts->offset + n + 7) / 8;
+    }
+    p.n = n;
+    p.limit = limit < 0 ? (uint64_t)INT64_MAX : (uint64_t)limit;
+    p.out = (void*)out->values;
+    p.out_valid = (uint8_t*)out->validity;
+    p.tiles = (n + kFillTile - 1) / kFillTile;
+    DevBuf<uint64_t> carry;
+    rc = carry.alloc((size_t)p.tiles * 8 * 2, s);
+    if (!rc) {
+        p.cj = carry;
+        p.cs = p.cj + p.tiles;
+        const bool rev = kind == PLGPU_FILL_BACKWARD;
+        if (eb == 8) {
+            if (rev) fill_launch<8, true>(p, s);
+            else fill_launch<8, false>(p, s);
+        } else {
+            if (rev) fill_launch<4, true>(p, s);
+            else fill_launch<4, false>(p, s);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = hip_fail(e, "fill");
+    }
+    if (rc) plgpu_column_release(out);
+    else out->null_count = -1;
+    return rc;
+}

@@ -23,7 +23,7 @@ class Expr:
 
     def __init__(self, kind: str, args: Sequence["Expr"] = (), op: str | None = None,
                  value: Any = None, name: str | None = None):
-        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | over | ...
+        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | fill | over | ...
         self.args = tuple(args)
         self.op = op
         self.value = value
@@ -74,6 +74,10 @@ class Expr:
             return f"{self.args[0]!r}.cum_{self.op}()"
         if self.kind == "lag":
             return f"{self.args[0]!r}.{self.op}{self.value}"
+        if self.kind == "fill":
+            if self.op in ("forward", "backward"):
+                return f"{self.args[0]!r}.{self.op}_fill(limit={self.value[0]!r})"
+            return f"{self.args[0]!r}.fill_null(strategy={self.op!r})"
         if self.kind == "over":
             keys = ", ".join(f'col("{k}")' for k in self.value)
             return f"{self.args[0]!r}.over([{keys}])"
@@ -163,11 +167,26 @@ class Expr:
         mode = "wrap" if wrap_numerical else ("strict" if strict else "non-strict")
         return Expr("cast", (self,), op=mode, value=dtype)
 
-    def fill_null(self, value: Any = None) -> "Expr":
-        """Expr.fill_null(value) (FunctionExpr::FillNull)."""
-        if value is None:
-            raise N.InvalidOperationError("fill_null needs a value (strategies are not supported on the GPU executor)")
-        return Expr("fill_null", (self, _to_expr(value)), op="fill_null")
+    def fill_null(self, value: Any = None, strategy: str | None = None, limit: Any = None) -> "Expr":
+        """Expr.fill_null(value) (FunctionExpr::FillNull), or
+        fill_null(strategy=..., limit=...) (FunctionExpr::FillNullWithStrategy):
+        forward / backward carry the closest non-null row over at most `limit`
+        nulls; min / max / mean / zero / one fill with the column's aggregate
+        or the constant."""
+        _fill_args(value, strategy, limit)
+        if value is None and strategy is None:
+            raise N.InvalidOperationError("fill_null needs a fill `value` or a `strategy`")
+        if value is not None:
+            return Expr("fill_null", (self, _to_expr(value)), op="fill_null")
+        return _fill(self, strategy, limit)
+
+    def forward_fill(self, limit: Any = None) -> "Expr":
+        """Expr.forward_fill: fill_null(strategy="forward", limit=limit)."""
+        return _fill(self, "forward", limit)
+
+    def backward_fill(self, limit: Any = None) -> "Expr":
+        """Expr.backward_fill: fill_null(strategy="backward", limit=limit)."""
+        return _fill(self, "backward", limit)
 
     def is_in(self, other: Sequence[Any], *, nulls_equal: bool = False) -> "Expr":
         """Expr.is_in over a literal collection: x == v0 | x == v1 | ...
@@ -208,8 +227,9 @@ class Expr:
                 "on the GPU executor")
         if _has_cum_lag(self):
             raise N.InvalidOperationError(
-                f"{self!r}.{op}(): a cumulative or lag function (cum_* / shift / diff) inside an aggregation's "
-                "input is not supported on the GPU executor")
+                f"{self!r}.{op}(): a cumulative, lag or fill function (cum_* / shift / diff / forward_fill / "
+                "backward_fill / fill_null(strategy=...)) inside an aggregation's input is not supported on the "
+                "GPU executor: it gives one value per row, in row order")
         return Expr("agg", (self,), op=op, value=value)
 
     def sum(self): return self._agg("sum")
@@ -302,7 +322,8 @@ class Expr:
         Takes `<elementwise>.rolling_*(...)`, the aggregations sum / mean /
         min / max / count / len / first / last / std / var of an elementwise
         expression (or pl.len()), and `<elementwise>.cum_*()` / `.shift(...)` /
-        `.diff(...)`, over plain key columns."""
+        `.diff(...)` / `.forward_fill(...)` / `.backward_fill(...)` /
+        `.fill_null(strategy=...)`, over plain key columns."""
         keys: list[str] = []
         items = [partition_by, *more_exprs]
         while items:
@@ -332,7 +353,7 @@ class Expr:
         f = self
         while f.kind == "alias":
             f = f.args[0]
-        if f.kind in ("rolling", "cum", "lag"):
+        if f.kind in ("rolling", "cum", "lag", "fill"):
             ok = _is_elementwise(f.args[0])
         elif f.kind == "agg":
             ok = f.op in _OVER_AGGS and _is_elementwise(f.args[0])
@@ -342,7 +363,8 @@ class Expr:
             raise N.InvalidOperationError(
                 f"{self!r}.over(...): the GPU executor evaluates over groups only rolling_* functions and the "
                 f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression, "
-                "and cum_sum / cum_min / cum_max / cum_count / shift / diff of an elementwise expression")
+                "and cum_sum / cum_min / cum_max / cum_count / shift / diff / forward_fill / backward_fill / "
+                "fill_null(strategy=...) of an elementwise expression")
         return Expr("over", (self,), op="over", value=tuple(keys))
 
     def sort(self, *, descending: bool = False, nulls_last: bool = False) -> "Expr":
@@ -366,11 +388,11 @@ def _rolling(e: Expr, kind: str, window_size: int, weights, min_samples, center,
 
 
 def _is_rowwise(e: Expr) -> bool:
-    """Elementwise expressions and rolling / cumulative / lag functions of them:
-    one value per row, in row order."""
+    """Elementwise expressions and rolling / cumulative / lag / fill functions of
+    them: one value per row, in row order."""
     if e.kind == "over":
         return True
-    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag") and builtins.all(_is_rowwise(a) for a in e.args)
+    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag", "fill") and builtins.all(_is_rowwise(a) for a in e.args)
 
 
 def _lag_input(e: Expr, what: str) -> None:
@@ -418,8 +440,50 @@ def _lag_fill(v: Any):
     return v
 
 
+_FILL_STRATEGIES = ("forward", "backward", "min", "max", "mean", "zero", "one")
+
+
+def _fill_args(value: Any, strategy: Any, limit: Any) -> None:
+    """The argument checks of py-polars' Expr.fill_null (expr.py:2916-2924)."""
+    if value is not None and strategy is not None:
+        raise ValueError("cannot specify both `value` and `strategy`")
+    if strategy not in ("forward", "backward") and limit is not None:
+        raise ValueError("can only specify `limit` when strategy is set to 'backward' or 'forward'")
+    if strategy is not None and strategy not in _FILL_STRATEGIES:
+        raise ValueError(f"invalid fill_null strategy {strategy!r}: expected one of {', '.join(_FILL_STRATEGIES)}")
+
+
+def _fill_limit(limit: Any):
+    """A literal `limit`: None or a non-negative integer (the reference's
+    limit is an unsigned IdxSize)."""
+    import operator
+
+    if isinstance(limit, Expr) and limit.kind == "lit":
+        limit = limit.value
+    if limit is None:
+        return None
+    if isinstance(limit, Expr):
+        raise N.InvalidOperationError(
+            f"fill limit={limit!r}: a computed `limit` is not supported on the GPU executor (pass an integer)")
+    try:
+        if isinstance(limit, bool):
+            raise TypeError
+        limit = operator.index(limit)
+    except TypeError:
+        raise N.InvalidOperationError(f"fill limit={limit!r}: `limit` must be a non-negative integer") from None
+    if limit < 0:
+        raise N.InvalidOperationError(f"fill limit={limit}: `limit` must be a non-negative integer (it is unsigned)")
+    return limit
+
+
+def _fill(e: Expr, strategy: str, limit: Any) -> Expr:
+    _fill_args(None, strategy, limit)
+    _lag_input(e, "fill_null" if strategy not in ("forward", "backward") else f"{strategy}_fill")
+    return Expr("fill", (e,), op=strategy, value=(_fill_limit(limit),))
+
+
 def _has_cum_lag(e: Expr) -> bool:
-    return e.kind in ("cum", "lag") or builtins.any(_has_cum_lag(a) for a in e.args)
+    return e.kind in ("cum", "lag", "fill") or builtins.any(_has_cum_lag(a) for a in e.args)
 
 
 _OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")

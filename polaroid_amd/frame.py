@@ -16,7 +16,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _native as N
-from .expr import Expr, _has_cum_lag, _has_over, _lag_n, col, lit, lower, to_instr_array
+from .expr import Expr, _fill_args, _fill_limit, _has_cum_lag, _has_over, _lag_n, col, lit, lower, to_instr_array
 
 
 # ------------------------------------------------------------------ dtypes
@@ -778,6 +778,112 @@ class Series:
                 "nulls changes the length of the column")
         return self._lag("diff", n)
 
+    # fill strategies (Series.forward_fill / backward_fill / fill_null) --------
+    def _fill(self, op: str, limit: Any = None, seg: "Series | None" = None) -> "Series":
+        """forward / backward fill on the device (plgpu_fill) over the 4- and
+        8-byte dtypes, the values moved as their bits; 1- and 2-byte integers
+        run as Int64 and back, a Categorical on its UInt32 codes with the
+        dictionary kept.  A column without a validity buffer is returned as it
+        is (fill_null.rs:61 returns a clone at null_count == 0).  `seg` (a
+        Boolean column of segment starts, Expr.over): no value crosses a start."""
+        limit = _fill_limit(limit)
+        cc = self._cat_codes()
+        if cc is not None:
+            return Series._categorical(self.name, cc[0], cc[1]._fill(op, limit, seg))
+        if self.dtype is String or self._col.dtype == N.BOOL:
+            raise N.InvalidOperationError(
+                f"{op}_fill of a {self.dtype} column is not supported on the GPU executor "
+                "(the fill kernel moves 4- and 8-byte values)")
+        if not self._col.validity:
+            return self.alias(self.name)
+        lg = self._logical_dtype()
+        phys = _BY_CODE[self._col.dtype]
+
+        def run(src: "Series") -> "Series":
+            out = N.Column()
+            N.check(N.lib().plgpu_fill(C.byref(src._col), None if seg is None else C.byref(seg._col), N.FILL[op],
+                                       -1 if limit is None else int(limit), C.byref(out), None))
+            return Series._from_native(self.name, out)
+
+        if phys in (Int8, Int16, UInt8, UInt16):
+            return run(self._cast_to(Int64))._cast_to(phys)
+        return run(self)._with_logical(lg)
+
+    def forward_fill(self, limit: Any = None) -> "Series":
+        return self._fill("forward", limit)
+
+    def backward_fill(self, limit: Any = None) -> "Series":
+        return self._fill("backward", limit)
+
+    def _physical_view(self) -> "Series":
+        """This column without its logical dtype (the same buffers)."""
+        s = self.alias(self.name)
+        s._logical = None
+        return s
+
+    def _fill_with(self, fill: "Series | int | float") -> "Series":
+        """Nulls replaced by a scalar or, row by row, by `fill`'s values (the
+        elementwise fill_null), the column's physical dtype kept."""
+        phys = _BY_CODE[self._col.dtype]
+        if phys is UInt64:  # (a literal above Int64's range: the same bits as Int64)
+            if not isinstance(fill, Series):
+                fill = int(fill) - (1 << 64) if int(fill) >= 1 << 63 else int(fill)
+            else:
+                fill = fill._reinterpret(Int64)
+            return self._reinterpret(Int64)._fill_with(fill)._reinterpret(UInt64).alias(self.name)
+        x = self._physical_view().alias("__x")
+        if isinstance(fill, Series):
+            e, df = col("__x").fill_null(col("__f")), DataFrame([x, fill._physical_view().alias("__f")])
+        else:
+            e, df = col("__x").fill_null(lit(fill)), DataFrame([x])
+        out = _eval(e, df)
+        if _BY_CODE[out._col.dtype] is not phys:
+            out = out._cast_wrap(phys) if phys in INTEGER_DTYPES and _BY_CODE[out._col.dtype] in INTEGER_DTYPES \
+                else out._cast_to(phys)
+        return out.alias(self.name)
+
+    def _fill_strategy(self, op: str, agg: "Series | None" = None) -> "Series":
+        """fill_null(strategy = zero / one / min / max / mean) lowered to what
+        exists (fill_null.rs:194 fill_null_numeric): a literal, or this
+        library's own global reduction (`agg` None) or per-row group aggregate
+        (`agg`, Expr.over), then the elementwise fill; an integer mean is
+        truncated toward zero to the column's dtype (NumCast::from, :210).
+        An all-null column or group stays as it is (:61-72)."""
+        if self.dtype is String or self._col.dtype == N.BOOL:
+            raise N.InvalidOperationError(
+                f"fill_null(strategy={op!r}) of a {self.dtype} column is not supported on the GPU executor")
+        lg = self._logical_dtype()
+        if op == "mean" and lg is not None:
+            raise N.InvalidOperationError(f"fill_null(strategy='mean') of a {lg} column is not supported")
+        phys = _BY_CODE[self._col.dtype]
+        if op in ("zero", "one"):
+            v = 1 if op == "one" else 0
+            return self._fill_with(float(v) if phys in FLOAT_DTYPES else v)._with_logical(lg)
+        if not self._col.validity:
+            return self.alias(self.name)
+        if agg is not None:
+            if _BY_CODE[agg._col.dtype] is not phys:
+                agg = agg._cast_to(phys)
+            return self._fill_with(agg)._with_logical(lg)
+        x = self._physical_view().alias("__x")
+        v = DataFrame([x]).select(getattr(col("__x"), op)())["__x"].to_list()[0]
+        if v is None:
+            return self.alias(self.name)
+        if phys in INTEGER_DTYPES:
+            v = int(v)
+        return self._fill_with(v)._with_logical(lg)
+
+    def fill_null(self, value: Any = None, strategy: str | None = None, limit: Any = None) -> "Series":
+        """Series.fill_null (fill_null.rs:58): a value, or a strategy."""
+        _fill_args(value, strategy, limit)
+        if value is None and strategy is None:
+            raise N.InvalidOperationError("fill_null needs a fill `value` or a `strategy`")
+        if value is not None:
+            return _eval(col(self.name).fill_null(value), DataFrame([self]))
+        if strategy in ("forward", "backward"):
+            return self._fill(strategy, limit)
+        return self._fill_strategy(strategy)
+
     # eager conveniences mirroring Series.filter ------------------------------
     def filter(self, mask: "Series") -> "Series":
         out = (N.Column * 1)()
@@ -1088,8 +1194,9 @@ class LazyFrame:
                 "compute it with with_columns first and filter on that column")
         if _has_cum_lag(pred):
             raise N.InvalidOperationError(
-                "a cumulative or lag function (cum_* / shift / diff) in a filter predicate is not supported on the "
-                "GPU executor: compute it with with_columns first and filter on that column")
+                "a cumulative, lag or fill function (cum_* / shift / diff / forward_fill / backward_fill / "
+                "fill_null(strategy=...)) in a filter predicate is not supported on the GPU executor: compute it "
+                "with with_columns first and filter on that column")
         return LazyFrame(("filter", self._node, pred))
 
     def group_by(self, *by: Any, maintain_order: bool = False) -> "LazyGroupBy":
@@ -1572,23 +1679,43 @@ def _over_rolling(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | Non
 
 
 def _cum_lag(f: Expr, vals: Series, seg: Series | None = None) -> Series:
-    """A "cum" / "lag" node on its evaluated input."""
+    """A "cum" / "lag" / "fill" node on its evaluated input."""
     if f.kind == "cum":
         return vals._cum(f.op, f.value[0], seg=seg)
+    if f.kind == "fill":
+        if f.op in ("forward", "backward"):
+            return vals._fill(f.op, f.value[0], seg=seg)
+        return vals._fill_strategy(f.op)
     return vals._lag(f.op, f.value[0], f.value[1] if f.op == "shift" else None, seg=seg)
 
 
 def _over_cum_lag(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
-    """<elementwise>.cum_*() / .shift(...) / .diff(...).over(keys), routed as
-    _over_rolling: presorted keys cost the segment starts and one kernel,
-    otherwise sort, gather, kernel and the gather back."""
+    """<elementwise>.cum_*() / .shift(...) / .diff(...) / .forward_fill(...) /
+    .backward_fill(...).over(keys), routed as _over_rolling: presorted keys
+    cost the segment starts and the function's kernels, otherwise sort,
+    gather, kernels and the gather back.  fill_null(strategy = zero / one) is
+    the plain fill; min / max / mean fill with the group's aggregate
+    (_over_agg) through the elementwise fill_null."""
     vals = _eval(f.args[0], df, cache)
+    if f.kind == "fill" and f.op not in ("forward", "backward"):
+        if f.op in ("zero", "one") or vals.dtype is String or vals._col.dtype == N.BOOL \
+                or (f.op == "mean" and vals._logical_dtype() is not None) or not vals._col.validity:
+            return vals._fill_strategy(f.op)  # (or its refusal)
+        if vals.len() != df.height:
+            raise N.ShapeError("over(): the partition keys and the values differ in length")
+        tmp = DataFrame([df._cols[k] for k in keys if k in df._cols] + [vals._physical_view().alias("__fill_x")])
+        return vals._fill_strategy(f.op, _over_agg(getattr(col("__fill_x"), f.op)(), keys, tmp))
+    cc = vals._cat_codes() if f.kind == "fill" else None
+    if cc is not None:  # a Categorical fills on its codes, the dictionary kept
+        vals = cc[1]
     starts, idx_s, inv = _over_segments(keys, df, cache)
     if starts.len() != vals.len():
         raise N.ShapeError("over(): the partition keys and the values differ in length")
     if idx_s is None:
-        return _cum_lag(f, vals, starts)
-    return _cum_lag(f, vals.gather(idx_s), starts).gather(inv)
+        res = _cum_lag(f, vals, starts)
+    else:
+        res = _cum_lag(f, vals.gather(idx_s), starts).gather(inv)
+    return Series._categorical(res.name, cc[0], res) if cc is not None else res
 
 
 def _over_agg(f: Expr, keys: Sequence[str], df: DataFrame) -> Series:
@@ -1612,7 +1739,7 @@ def _cum_lag_below(e: Expr, top: bool = True) -> bool:
     """Is a cum / lag node anywhere but at the top (under its alias) of e?"""
     if e.kind == "alias":
         return _cum_lag_below(e.args[0], top)
-    if e.kind in ("cum", "lag") and not top:
+    if e.kind in ("cum", "lag", "fill") and not top:
         return True
     return builtins.any(_cum_lag_below(a, False) for a in e.args)
 
@@ -1627,14 +1754,14 @@ def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list, top: boo
             f = f.args[0]
         if f.kind == "rolling":
             res = _over_rolling(f, e.value, df, cache)
-        elif f.kind in ("cum", "lag"):
+        elif f.kind in ("cum", "lag", "fill"):
             res = _over_cum_lag(f, e.value, df, cache)
         else:
             res = _over_agg(f, e.value, df)
         name = f"__over{builtins.len(extra)}"
         extra.append(res.alias(name))
         return col(name)
-    if e.kind in ("cum", "lag") and not top:
+    if e.kind in ("cum", "lag", "fill") and not top:
         # inside a larger expression (x / x.shift(1) - 1): a temporary column too
         res = _cum_lag(e, _eval(e.args[0], df, cache))
         name = f"__over{builtins.len(extra)}"
@@ -1678,7 +1805,7 @@ def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
         else:
             res = inner.sort(descending=base.value[0], nulls_last=base.value[1])
         return res.alias(expr.output_name())
-    if base.kind in ("cum", "lag"):
+    if base.kind in ("cum", "lag", "fill"):
         return _cum_lag(base, _eval(base.args[0], df)).alias(expr.output_name())
     expr, df = _lower_strings(expr, df)
     name = expr.output_name()
@@ -1827,10 +1954,11 @@ def _gb_lower(df: DataFrame, key: str | tuple | None, aggs: list[Expr], pred: Ex
             exprs.append(x)
             specs.append((base.op, ("input", builtins.len(exprs) - 1)))
             out_logical.append(lg if base.op in ("min", "max", "first", "last", "sum") else None)
-        elif base.kind in ("cum", "lag"):
+        elif base.kind in ("cum", "lag", "fill"):
             raise N.InvalidOperationError(
-                f"{e!r} is not an aggregation: cum_* / shift / diff give one value per row and are not supported "
-                "inside group_by().agg() on the GPU executor (use .over(keys) in with_columns)")
+                f"{e!r} is not an aggregation: cum_* / shift / diff / forward_fill / backward_fill / "
+                "fill_null(strategy=...) give one value per row and are not supported inside group_by().agg() on "
+                "the GPU executor (use .over(keys) in with_columns)")
         else:
             raise N.InvalidOperationError(
                 f"aggregation {e!r} is not supported on the GPU executor "

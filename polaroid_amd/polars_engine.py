@@ -68,7 +68,7 @@ _BOOLFUNCS: dict[str, Callable[[Expr], Expr]] = {
 
 
 _CUM_LAG_FUNCS = frozenset({"cum_sum", "cum_min", "cum_max", "cum_count", "cum_prod", "shift", "shift_and_fill",
-                            "diff", "pct_change"})
+                            "diff", "pct_change", "fill_null_with_strategy"})
 
 
 _CUM_LAG_REFUSED = {
@@ -77,6 +77,7 @@ _CUM_LAG_REFUSED = {
     "cum_max": ("String", "Boolean", "Time"),
     "shift": ("String", "Boolean", "Time"),
     "diff": ("String", "Boolean", "Date", "Time"),
+    "fill_null_with_strategy": ("String", "Boolean", "Time"),
 }
 
 
@@ -216,7 +217,10 @@ class _Translator:
         """FunctionExpr::CumSum / CumMin / CumMax / CumCount (function_data
         (name, reverse), expr_nodes.rs:1265-1269), Shift / ShiftAndFill with
         inputs [x, n] / [x, n, fill] (:1223-1224) and Diff (("diff",
-        null_behavior), inputs [x, n], :1280) -> Expr.cum_* / shift / diff."""
+        null_behavior), inputs [x, n], :1280) -> Expr.cum_* / shift / diff;
+        FillNullWithStrategy (("fill_null_with_strategy", strategy, limit),
+        inputs [x], :1385: the limit arrives in the tuple) -> Expr.fill_null(
+        strategy=..., limit=...)."""
         if fname in ("cum_prod", "pct_change"):
             raise Unsupported(f"function {fname} (not built on the GPU executor)")
         if self._schema is None:
@@ -224,17 +228,33 @@ class _Translator:
             # below an aggregation or in a filter predicate
             raise Unsupported(f"function {fname} outside the expressions of a select / with_columns")
         kind = self.expr_kind(e.input[0], self._schema)
-        # every input dtype the Series layer refuses (frame.Series._cum / _lag) is gated here, from the scan
-        # schema, so such a query stays on polars instead of failing at collect time
+        # every input dtype the Series layer refuses (frame.Series._cum / _lag / _fill) is gated here, from the
+        # scan schema, so such a query stays on polars instead of failing at collect time
         base = "shift" if fname == "shift_and_fill" else fname
+        strategy = str(fd[1]) if fname == "fill_null_with_strategy" and len(fd) > 1 else None
+        if strategy in ("forward", "backward") and kind == "String":
+            # a Categorical column fills on its codes; a String one is refused
+            x0 = self.view(e.input[0])
+            if _name(x0) == "Column" and _dtype_kind(self._schema.get(str(x0.name))) in ("Categorical", "Enum"):
+                kind = "Categorical"
         if kind in _CUM_LAG_REFUSED.get(base, ()):
-            raise Unsupported(f"{fname} of a {kind} input")
+            raise Unsupported(f"{'fill_null' if strategy else fname} of a {kind} input")
+        if strategy == "mean" and kind in ("Date", "Datetime", "Duration"):
+            raise Unsupported(f"fill_null(strategy='mean') of a {kind} input")
         held, self._schema = self._schema, None  # (no window in the function's own input)
         try:
             x = self.expr(e.input[0])
         finally:
             self._schema = held
         try:
+            if strategy is not None:
+                limit = fd[2] if len(fd) > 2 else None
+                try:
+                    return x.fill_null(strategy=strategy, limit=limit)
+                except ValueError as exc:
+                    raise Unsupported(str(exc)) from exc
+            if fname == "fill_null_with_strategy":
+                raise Unsupported("fill_null_with_strategy without a strategy")
             if fname.startswith("cum_"):
                 if len(fd) > 1 and fd[1]:
                     raise Unsupported(f"{fname} with reverse=True")
