@@ -214,7 +214,9 @@ typedef struct plgpu_groupby_info {
     int32_t part_layout;         /* partitioned path: partition bits | scatter passes << 8 (0: not partitioned) */
     int32_t fused_variant;       /* the gb_fast_kernel instantiation the fused path launched (0: it did not
                                     run, i.e. path 0 or 3): bits 0-2 VAR, 3-4 PACK, 5 NULLS, 6 RUNS, 7 DERIV,
-                                    8-9 LIMBS, 10-12 NACC, 13 PRED, 14 SUMONLY, 15 always 1, 16-19 ROWS */
+                                    8-9 LIMBS, 10-12 NACC, 13 PRED, 14 SUMONLY, 15 always 1, 16-19 ROWS,
+                                    20 a NULLS instantiation read its validity as whole words per wave
+                                    (every bitmap 8-byte aligned at a column offset that is a multiple of 64) */
     int32_t _reserved;           /* 0 (keeps the size a multiple of 8 without implicit padding) */
 } plgpu_groupby_info;
 

@@ -105,13 +105,14 @@ def fused_variant(info) -> dict:
     collect(info=...) filled, or the raw value): the template arguments of the
     gb_fast_kernel instantiation the call launched.  "ran" is False, and the
     rest 0, when the fused kernel did not run (the generic or the partitioned
-    path)."""
+    path).  "vwords": a NULLS instantiation read its validity as whole words
+    per wave (GbParams::vwords), not one byte per row pair and column."""
     v = info if isinstance(info, int) else (
         info["fused_variant"] if isinstance(info, dict) else info.fused_variant)
     return {"var": v & 7, "pack": (v >> 3) & 3, "nulls": bool((v >> 5) & 1), "runs": bool((v >> 6) & 1),
             "deriv": bool((v >> 7) & 1), "limbs": (v >> 8) & 3, "nacc": (v >> 10) & 7,
             "pred": (v >> 13) & 1, "sumonly": bool((v >> 14) & 1), "rows": (v >> 16) & 15,
-            "ran": bool((v >> 15) & 1)}
+            "ran": bool((v >> 15) & 1), "vwords": bool((v >> 20) & 1)}
 
 
 # Every symbol declared in include/polaroid_gpu.h, with its signature.

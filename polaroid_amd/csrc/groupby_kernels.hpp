@@ -2002,7 +2002,8 @@ hipError_t launch_fast_rows(const Plan& pl, const DevProgram& dp, hipStream_t s)
     pl.launched_var = VAR == 1 || VAR == 4;
     static_assert(VAR < 8 && PACK < 4 && LIMBS < 4 && NACC < 8 && PRED < 2 && ROWS < 16, "fused_variant's fields");
     pl.launched_variant = VAR | PACK << 3 | (NULLS ? 1 : 0) << 5 | (RUNS ? 1 : 0) << 6 | (DERIV ? 1 : 0) << 7 |
-                          LIMBS << 8 | NACC << 10 | PRED << 13 | (SUMONLY ? 1 : 0) << 14 | 1 << 15 | ROWS << 16;
+                          LIMBS << 8 | NACC << 10 | PRED << 13 | (SUMONLY ? 1 : 0) << 14 | 1 << 15 | ROWS << 16 |
+                          (NULLS && q.vwords ? 1 : 0) << 20;
     if (pl.local) {
         const int64_t tile = (int64_t)kGbThreads * ROWS;
         const int64_t nall = q.n_full / tile + (pl.p.n > q.n_full ? 1 : 0);
