@@ -917,6 +917,38 @@ enum plgpu_fill_kind { PLGPU_FILL_FORWARD = 1, PLGPU_FILL_BACKWARD = 2 };
 int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_starts /* NULL: one segment */,
                int32_t kind, int64_t limit /* < 0: no limit */, plgpu_column* out, void* stream);
 
+/* ---- exponentially weighted mean -----------------------------------------------
+ * plgpu_ewm_mean: the exponentially weighted mean of a Float32 / Float64
+ * column, restarted at every set bit of seg_starts (NULL: one segment; else a
+ * null-free Boolean column of the values' length, as plgpu_segment_starts
+ * writes it).  Replaces polars-compute/src/ewm/mean.rs:52
+ * EwmMeanState::update_iter (through polars-ops/src/series/ops/ewm.rs:11
+ * ewm_mean and polars-expr/src/dispatch/misc.rs:887) and, with seg_starts, its
+ * evaluation on every group's rows (polars-expr/src/expressions/window.rs:356,
+ * GroupsToRows).  The state (mean, weight, count) is zero at the start of a
+ * segment; its first non-null row sets mean = x, weight = 1; every other row
+ * multiplies weight by 1 - alpha when it is non-null or ignore_nulls is 0, and
+ * a non-null row then does mean += (x - mean) * v / (weight + v) with v = 1
+ * (adjust; weight += 1) or alpha (no adjust; weight = 1).  A row is non-null
+ * in the output when it is non-null in the input and the segment has seen at
+ * least max(min_samples, 1) non-null rows.  The dtype is kept; Float32 is
+ * computed in double and rounded once.
+ * Non-finite values: the first NaN / +inf / -inf among the non-null values of
+ * a column or segment comes out as itself, every later non-null row of that
+ * segment is NaN (the reference's x - mean); a segment start clears this.
+ * The first non-null row of a segment equals its input bit for bit; other rows
+ * agree with the reference's sequential fold within the bound DESIGN.md "Float
+ * tolerance against the reference" states (a scan rounds in tree order).
+ * PLGPU_ERR_INVALID: a NULL values / out, alpha outside (0, 1] or NaN, a
+ * negative min_samples, a seg_starts that is not a null-free Boolean column of
+ * the values' length; PLGPU_ERR_SCHEMA: any other dtype; both before any
+ * device work.  n == 0 is legal.
+ * Three launches (tile reduce, scan of the tile summaries, apply); no
+ * workgroup waits on another. */
+int plgpu_ewm_mean(const plgpu_column* values, const plgpu_column* seg_starts /* NULL: one segment */,
+                   double alpha, int32_t adjust, int32_t ignore_nulls, int64_t min_samples,
+                   plgpu_column* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,7 @@ SIGNATURES = {
     "plgpu_cumulative": (C.c_int, [_COLP, _COLP, C.c_int32, _COLP, _P]),
     "plgpu_lag": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _COLP, _P]),
     "plgpu_fill": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, _COLP, _P]),
+    "plgpu_ewm_mean": (C.c_int, [_COLP, _COLP, C.c_double, C.c_int32, C.c_int32, C.c_int64, _COLP, _P]),
 }
 
 GB_MAX_ACC = 6
@@ -224,6 +225,8 @@ LAG = {"shift": 1, "diff": 2}
 FILL = {"forward": 1, "backward": 2}
 CUM_BLOCK = 2048            # kCumBlock (csrc/cumulative.hip): rows of one workgroup scan
 CUM_TILE = 8 * CUM_BLOCK    # kCumTile: rows per workgroup of the scan kernels (one summary / carry each)
+CUM_THREADS = 256           # kCumThreads / kEwmThreads: threads of a tile's workgroup (CUM_BLOCK / 256 rows each)
+CUM_TOTALS_THREADS = 1024   # kCumTotalsThreads / kEwmTotalsThreads: threads of the one workgroup that scans the summaries
 
 _lib = None
 

@@ -23,7 +23,7 @@ class Expr:
 
     def __init__(self, kind: str, args: Sequence["Expr"] = (), op: str | None = None,
                  value: Any = None, name: str | None = None):
-        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | fill | over | ...
+        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | fill | ewm | over | ...
         self.args = tuple(args)
         self.op = op
         self.value = value
@@ -78,6 +78,10 @@ class Expr:
             if self.op in ("forward", "backward"):
                 return f"{self.args[0]!r}.{self.op}_fill(limit={self.value[0]!r})"
             return f"{self.args[0]!r}.fill_null(strategy={self.op!r})"
+        if self.kind == "ewm":
+            alpha, adjust, min_samples, ignore_nulls = self.value
+            return (f"{self.args[0]!r}.ewm_{self.op}(alpha={alpha!r}, adjust={adjust}, min_samples={min_samples}, "
+                    f"ignore_nulls={ignore_nulls})")
         if self.kind == "over":
             keys = ", ".join(f'col("{k}")' for k in self.value)
             return f"{self.args[0]!r}.over([{keys}])"
@@ -227,9 +231,9 @@ class Expr:
                 "on the GPU executor")
         if _has_cum_lag(self):
             raise N.InvalidOperationError(
-                f"{self!r}.{op}(): a cumulative, lag or fill function (cum_* / shift / diff / forward_fill / "
-                "backward_fill / fill_null(strategy=...)) inside an aggregation's input is not supported on the "
-                "GPU executor: it gives one value per row, in row order")
+                f"{self!r}.{op}(): a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / "
+                "backward_fill / fill_null(strategy=...) / ewm_mean) inside an aggregation's input is not supported "
+                "on the GPU executor: it gives one value per row, in row order")
         return Expr("agg", (self,), op=op, value=value)
 
     def sum(self): return self._agg("sum")
@@ -314,6 +318,30 @@ class Expr:
                 "nulls changes the length of the column")
         return Expr("lag", (self,), op="diff", value=(_lag_n(n, "diff"),))
 
+    def ewm_mean(self, *, com: float | None = None, span: float | None = None, half_life: float | None = None,
+                 alpha: float | None = None, adjust: bool = True, min_samples: int = 1,
+                 ignore_nulls: bool = False) -> "Expr":
+        """Exponentially weighted mean (Expr.ewm_mean; polars-compute/src/ewm/
+        mean.rs:52): Float32 stays Float32, every other numeric dtype gives
+        Float64."""
+        a = _prepare_alpha(com, span, half_life, alpha)
+        _lag_input(self, "ewm_mean")
+        return Expr("ewm", (self,), op="mean", value=(a, bool(adjust), _ewm_min_samples(min_samples),
+                                                      bool(ignore_nulls)))
+
+    def ewm_std(self, *args: Any, **kwargs: Any) -> "Expr":
+        raise N.InvalidOperationError(
+            "ewm_std is not built on the GPU executor (only ewm_mean is; the variance carries a different state)")
+
+    def ewm_var(self, *args: Any, **kwargs: Any) -> "Expr":
+        raise N.InvalidOperationError(
+            "ewm_var is not built on the GPU executor (only ewm_mean is; the variance carries a different state)")
+
+    def ewm_mean_by(self, *args: Any, **kwargs: Any) -> "Expr":
+        raise N.InvalidOperationError(
+            "ewm_mean_by is not built on the GPU executor (only ewm_mean is; time-based decay carries a "
+            "different state)")
+
     def over(self, partition_by: Any, *more_exprs: Any, order_by: Any = None,
              mapping_strategy: str = "group_to_rows") -> "Expr":
         """Expr.over: evaluate this expression on every group of the partition
@@ -323,7 +351,7 @@ class Expr:
         min / max / count / len / first / last / std / var of an elementwise
         expression (or pl.len()), and `<elementwise>.cum_*()` / `.shift(...)` /
         `.diff(...)` / `.forward_fill(...)` / `.backward_fill(...)` /
-        `.fill_null(strategy=...)`, over plain key columns."""
+        `.fill_null(strategy=...)` / `.ewm_mean(...)`, over plain key columns."""
         keys: list[str] = []
         items = [partition_by, *more_exprs]
         while items:
@@ -353,7 +381,7 @@ class Expr:
         f = self
         while f.kind == "alias":
             f = f.args[0]
-        if f.kind in ("rolling", "cum", "lag", "fill"):
+        if f.kind in ("rolling", "cum", "lag", "fill", "ewm"):
             ok = _is_elementwise(f.args[0])
         elif f.kind == "agg":
             ok = f.op in _OVER_AGGS and _is_elementwise(f.args[0])
@@ -364,7 +392,7 @@ class Expr:
                 f"{self!r}.over(...): the GPU executor evaluates over groups only rolling_* functions and the "
                 f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression, "
                 "and cum_sum / cum_min / cum_max / cum_count / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...) of an elementwise expression")
+                "fill_null(strategy=...) / ewm_mean of an elementwise expression")
         return Expr("over", (self,), op="over", value=tuple(keys))
 
     def sort(self, *, descending: bool = False, nulls_last: bool = False) -> "Expr":
@@ -388,11 +416,11 @@ def _rolling(e: Expr, kind: str, window_size: int, weights, min_samples, center,
 
 
 def _is_rowwise(e: Expr) -> bool:
-    """Elementwise expressions and rolling / cumulative / lag / fill functions of
+    """Elementwise expressions and rolling / cumulative / lag / fill / ewm functions of
     them: one value per row, in row order."""
     if e.kind == "over":
         return True
-    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag", "fill") and builtins.all(_is_rowwise(a) for a in e.args)
+    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag", "fill", "ewm") and builtins.all(_is_rowwise(a) for a in e.args)
 
 
 def _lag_input(e: Expr, what: str) -> None:
@@ -483,7 +511,48 @@ def _fill(e: Expr, strategy: str, limit: Any) -> Expr:
 
 
 def _has_cum_lag(e: Expr) -> bool:
-    return e.kind in ("cum", "lag", "fill") or builtins.any(_has_cum_lag(a) for a in e.args)
+    return e.kind in ("cum", "lag", "fill", "ewm") or builtins.any(_has_cum_lag(a) for a in e.args)
+
+
+def _prepare_alpha(com: Any = None, span: Any = None, half_life: Any = None, alpha: Any = None) -> float:
+    """The decay of an ewm_* function as its smoothing factor alpha, with the
+    checks and messages of py-polars' _prepare_alpha (expr.py:11710)."""
+    import math
+
+    given = [v for v in (com, span, half_life, alpha) if v is not None]
+    if builtins.len(given) > 1:
+        raise ValueError("parameters `com`, `span`, `half_life`, and `alpha` are mutually exclusive")
+    if not given:
+        raise ValueError("one of `com`, `span`, `half_life`, or `alpha` must be set")
+    if com is not None:
+        if not com >= 0.0:
+            raise ValueError(f"require `com` >= 0 (found {com!r})")
+        return 1.0 / (1.0 + com)
+    if span is not None:
+        if not span >= 1.0:
+            raise ValueError(f"require `span` >= 1 (found {span!r})")
+        return 2.0 / (span + 1.0)
+    if half_life is not None:
+        if not half_life > 0.0:
+            raise ValueError(f"require `half_life` > 0 (found {half_life!r})")
+        return 1.0 - math.exp(-math.log(2.0) / half_life)
+    if not 0 < alpha <= 1:
+        raise ValueError(f"require 0 < `alpha` <= 1 (found {alpha!r})")
+    return float(alpha)
+
+
+def _ewm_min_samples(v: Any) -> int:
+    import operator
+
+    try:
+        if isinstance(v, bool):
+            raise TypeError
+        v = operator.index(v)
+    except TypeError:
+        raise N.InvalidOperationError(f"ewm_mean(min_samples={v!r}): `min_samples` must be an integer") from None
+    if v < 0:
+        raise N.InvalidOperationError(f"ewm_mean(min_samples={v}): `min_samples` must be a non-negative integer")
+    return v
 
 
 _OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")

@@ -16,7 +16,8 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _native as N
-from .expr import Expr, _fill_args, _fill_limit, _has_cum_lag, _has_over, _lag_n, col, lit, lower, to_instr_array
+from .expr import (Expr, _ewm_min_samples, _fill_args, _fill_limit, _has_cum_lag, _has_over, _lag_n, _prepare_alpha,
+                   col, lit, lower, to_instr_array)
 
 
 # ------------------------------------------------------------------ dtypes
@@ -815,6 +816,31 @@ class Series:
     def backward_fill(self, limit: Any = None) -> "Series":
         return self._fill("backward", limit)
 
+    # exponentially weighted mean (Series.ewm_mean) ----------------------------
+    def _ewm_mean(self, alpha: float, adjust: bool, min_samples: int, ignore_nulls: bool,
+                  seg: "Series | None" = None) -> "Series":
+        """ewm_mean on the device (plgpu_ewm_mean): Float64 and Float32 keep
+        their dtype, every integer dtype is cast to Float64 first
+        (function_expr/schema.rs:417 map_numeric_to_float_dtype).  `seg` (a
+        Boolean column of segment starts, Expr.over): the state restarts at
+        every start."""
+        if self._cat_codes() is not None or self.dtype is String or self._col.dtype == N.BOOL \
+                or self._logical_dtype() is not None:
+            raise N.InvalidOperationError(f"ewm_mean of a {self.dtype} column is not supported: the input must be numeric")
+        phys = _BY_CODE[self._col.dtype]
+        src = self if phys in FLOAT_DTYPES else self._cast_to(Float64)
+        out = N.Column()
+        N.check(N.lib().plgpu_ewm_mean(C.byref(src._col), None if seg is None else C.byref(seg._col), float(alpha),
+                                       int(bool(adjust)), int(bool(ignore_nulls)), int(min_samples), C.byref(out),
+                                       None))
+        return Series._from_native(self.name, out)
+
+    def ewm_mean(self, *, com: float | None = None, span: float | None = None, half_life: float | None = None,
+                 alpha: float | None = None, adjust: bool = True, min_samples: int = 1,
+                 ignore_nulls: bool = False) -> "Series":
+        return self._ewm_mean(_prepare_alpha(com, span, half_life, alpha), adjust, _ewm_min_samples(min_samples),
+                              ignore_nulls)
+
     def _physical_view(self) -> "Series":
         """This column without its logical dtype (the same buffers)."""
         s = self.alias(self.name)
@@ -1194,8 +1220,8 @@ class LazyFrame:
                 "compute it with with_columns first and filter on that column")
         if _has_cum_lag(pred):
             raise N.InvalidOperationError(
-                "a cumulative, lag or fill function (cum_* / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...)) in a filter predicate is not supported on the GPU executor: compute it "
+                "a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / backward_fill / "
+                "fill_null(strategy=...) / ewm_mean) in a filter predicate is not supported on the GPU executor: compute it "
                 "with with_columns first and filter on that column")
         return LazyFrame(("filter", self._node, pred))
 
@@ -1679,9 +1705,11 @@ def _over_rolling(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | Non
 
 
 def _cum_lag(f: Expr, vals: Series, seg: Series | None = None) -> Series:
-    """A "cum" / "lag" / "fill" node on its evaluated input."""
+    """A "cum" / "lag" / "fill" / "ewm" node on its evaluated input."""
     if f.kind == "cum":
         return vals._cum(f.op, f.value[0], seg=seg)
+    if f.kind == "ewm":
+        return vals._ewm_mean(*f.value, seg=seg)
     if f.kind == "fill":
         if f.op in ("forward", "backward"):
             return vals._fill(f.op, f.value[0], seg=seg)
@@ -1739,7 +1767,7 @@ def _cum_lag_below(e: Expr, top: bool = True) -> bool:
     """Is a cum / lag node anywhere but at the top (under its alias) of e?"""
     if e.kind == "alias":
         return _cum_lag_below(e.args[0], top)
-    if e.kind in ("cum", "lag", "fill") and not top:
+    if e.kind in ("cum", "lag", "fill", "ewm") and not top:
         return True
     return builtins.any(_cum_lag_below(a, False) for a in e.args)
 
@@ -1754,14 +1782,14 @@ def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list, top: boo
             f = f.args[0]
         if f.kind == "rolling":
             res = _over_rolling(f, e.value, df, cache)
-        elif f.kind in ("cum", "lag", "fill"):
+        elif f.kind in ("cum", "lag", "fill", "ewm"):
             res = _over_cum_lag(f, e.value, df, cache)
         else:
             res = _over_agg(f, e.value, df)
         name = f"__over{builtins.len(extra)}"
         extra.append(res.alias(name))
         return col(name)
-    if e.kind in ("cum", "lag", "fill") and not top:
+    if e.kind in ("cum", "lag", "fill", "ewm") and not top:
         # inside a larger expression (x / x.shift(1) - 1): a temporary column too
         res = _cum_lag(e, _eval(e.args[0], df, cache))
         name = f"__over{builtins.len(extra)}"
@@ -1805,7 +1833,7 @@ def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
         else:
             res = inner.sort(descending=base.value[0], nulls_last=base.value[1])
         return res.alias(expr.output_name())
-    if base.kind in ("cum", "lag", "fill"):
+    if base.kind in ("cum", "lag", "fill", "ewm"):
         return _cum_lag(base, _eval(base.args[0], df)).alias(expr.output_name())
     expr, df = _lower_strings(expr, df)
     name = expr.output_name()
@@ -1954,10 +1982,10 @@ def _gb_lower(df: DataFrame, key: str | tuple | None, aggs: list[Expr], pred: Ex
             exprs.append(x)
             specs.append((base.op, ("input", builtins.len(exprs) - 1)))
             out_logical.append(lg if base.op in ("min", "max", "first", "last", "sum") else None)
-        elif base.kind in ("cum", "lag", "fill"):
+        elif base.kind in ("cum", "lag", "fill", "ewm"):
             raise N.InvalidOperationError(
                 f"{e!r} is not an aggregation: cum_* / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...) give one value per row and are not supported inside group_by().agg() on "
+                "fill_null(strategy=...) / ewm_mean give one value per row and are not supported inside group_by().agg() on "
                 "the GPU executor (use .over(keys) in with_columns)")
         else:
             raise N.InvalidOperationError(
