@@ -223,10 +223,11 @@ ROLLING = {"sum": 1, "mean": 2, "min": 3, "max": 4, "var": 5, "std": 6}
 CUM = {"sum": 1, "min": 2, "max": 3, "count": 4}
 LAG = {"shift": 1, "diff": 2}
 FILL = {"forward": 1, "backward": 2}
-CUM_BLOCK = 2048            # kCumBlock (csrc/cumulative.hip): rows of one workgroup scan
-CUM_TILE = 8 * CUM_BLOCK    # kCumTile: rows per workgroup of the scan kernels (one summary / carry each)
-CUM_THREADS = 256           # kCumThreads / kEwmThreads: threads of a tile's workgroup (CUM_BLOCK / 256 rows each)
-CUM_TOTALS_THREADS = 1024   # kCumTotalsThreads / kEwmTotalsThreads: threads of the one workgroup that scans the summaries
+# The tile geometry of the segmented scans (csrc/seg_scan.hpp; cumulative, fill and ewm share it)
+CUM_BLOCK = 2048            # kTileBlock: rows of one workgroup scan
+CUM_TILE = 8 * CUM_BLOCK    # kTileRows: rows per workgroup of the scan kernels (one summary / carry each)
+CUM_THREADS = 256           # kTileThreads: threads of a tile's workgroup (CUM_BLOCK / 256 rows each)
+CUM_TOTALS_THREADS = 1024   # kTotalsThreads: threads of the one workgroup that scans the summaries
 
 _lib = None
 

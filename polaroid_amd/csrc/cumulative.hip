@@ -11,7 +11,7 @@
 //
 // MI355X design (DESIGN.md "Cumulative and lag expressions"): three launches,
 // none of which waits on another workgroup.  cum_reduce_kernel: one workgroup
-// per tile of kCumTile rows writes the tile's summary (does it hold a segment
+// per tile of kTileRows rows writes the tile's summary (does it hold a segment
 // start; the aggregate of the rows after its last start, or of all its rows;
 // for f64 sums the non-finite flags and the exponent range).
 // cum_totals_kernel: one workgroup scans the summaries with the segmented
@@ -19,8 +19,8 @@
 // every tile's carry in their place; for f64 sums it first fixes the column's
 // bottom exponent, shifts every tile's sum onto it and checks the span.
 // cum_apply_kernel re-reads the tile, scans it and adds the carry to the rows
-// before the tile's first start.  A workgroup takes its tile as kCumBlocks
-// block scans of kCumBlock rows one after the other, the running value handed
+// before the tile's first start.  A workgroup takes its tile as kTileBlocks
+// block scans of kTileBlock rows one after the other, the running value handed
 // from one to the next in registers, so the column has an eighth of the
 // summaries one scan per workgroup would leave to the single-workgroup launch.
 //
@@ -37,16 +37,12 @@
 #include <string>
 
 #include "plgpu_internal.hpp"
+#include "seg_scan.hpp"
+#include "seg_starts.hpp"
 
 namespace plgpu {
 namespace {
 
-constexpr int kCumThreads = 256;
-constexpr int kCumPer = 8;                         // consecutive rows per thread
-constexpr int kCumBlock = kCumThreads * kCumPer;   // rows of one workgroup scan
-constexpr int kCumBlocks = 8;                      // scans a workgroup runs one after the other
-constexpr int kCumTile = kCumBlock * kCumBlocks;   // rows per workgroup (polaroid_amd/_native.py CUM_TILE)
-constexpr int kCumTotalsThreads = 1024;
 constexpr int kCumSpan = kSumWindowBits - 53;      // binades between the smallest and largest exponent
 
 enum CumK : int { CK_SUMI = 0, CK_SUMF = 1, CK_MM = 2, CK_COUNT = 3 };
@@ -123,53 +119,14 @@ __device__ __forceinline__ St st_shfl_up(const St& x, int off) {
     return y;
 }
 
-// (flag, value) (+) (flag, value) of the segmented scan.
+// The operator of the segmented scan (seg_scan.hpp).
 template <int K, bool WORDS>
-__device__ __forceinline__ void seg_comb(bool& lf, St& l, bool rf, const St& r) {
-    l = rf ? r : st_comb<K, WORDS>(l, r);
-    lf = lf || rf;
-}
-
-// Segmented scan of one (flag, value) per thread over the workgroup: the
-// exclusive prefix of this thread in (ef, ev), the workgroup's total in
-// (tf, tv).  wv / wf: one slot per wave.
-template <int K, bool WORDS>
-__device__ __forceinline__ void block_seg_scan(bool f, const St& v, St* wv, uint32_t* wf, bool& ef, St& ev, bool& tf,
-                                               St& tv) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    St x = v;
-    uint32_t xf = f ? 1u : 0u;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const St y = st_shfl_up<K>(x, off);
-        const uint32_t yf = __shfl_up(xf, off, 64);
-        if (lane >= off) {
-            if (!xf) x = st_comb<K, WORDS>(y, x);
-            xf |= yf;
-        }
-    }
-    if (lane == 63) {
-        wv[wid] = x;
-        wf[wid] = xf;
-    }
-    St px = st_shfl_up<K>(x, 1);
-    uint32_t pf = __shfl_up(xf, 1, 64);
-    if (lane == 0) {
-        px = st_id();
-        pf = 0u;
-    }
-    __syncthreads();
-    ef = false;
-    ev = st_id();
-    tf = false;
-    tv = st_id();
-    for (int w = 0; w < nw; ++w) {
-        if (w < wid) seg_comb<K, WORDS>(ef, ev, wf[w] != 0u, wv[w]);
-        seg_comb<K, WORDS>(tf, tv, wf[w] != 0u, wv[w]);
-    }
-    seg_comb<K, WORDS>(ef, ev, pf != 0u, px);
-    __syncthreads();
-}
+struct CumOp {
+    using T = St;
+    static __device__ __forceinline__ St id() { return st_id(); }
+    static __device__ __forceinline__ St comb(const St& l, const St& r) { return st_comb<K, WORDS>(l, r); }
+    static __device__ __forceinline__ St shfl_up(const St& x, int off) { return st_shfl_up<K>(x, off); }
+};
 
 // Smallest / largest of one (lo, hi) pair per thread over the workgroup.
 __device__ __forceinline__ void block_minmax(int& lo, int& hi, int* slo, int* shi) {
@@ -193,9 +150,9 @@ __device__ __forceinline__ void block_minmax(int& lo, int& hi, int* slo, int* sh
     __syncthreads();
 }
 
-// The thread's kCumPer rows: register forms, validity bits, segment-start bits.
+// The thread's kTilePer rows: register forms, validity bits, segment-start bits.
 struct CumRows {
-    uint64_t x[kCumPer];
+    uint64_t x[kTilePer];
     uint32_t vm;  // bit k: row k is inside the column and not null
     uint32_t sb;  // bit k: row k starts a segment
 };
@@ -204,23 +161,17 @@ template <bool SEG>
 __device__ __forceinline__ void cum_load(const CumParams& p, int64_t base, CumRows& r) {
     r.vm = 0u;
     r.sb = 0u;
-    const bool full = base + kCumPer <= p.n;
+    const bool full = base + kTilePer <= p.n;
     const bool wide = p.c.dtype == PLGPU_F64 || p.c.dtype == PLGPU_I64 || p.c.dtype == PLGPU_U64;
     const uint64_t* src = (const uint64_t*)p.c.values + p.c.offset + base;
     if (wide && full && ((uintptr_t)src & 15u) == 0) {
-        const ulonglong2* s2 = (const ulonglong2*)src;
-#pragma unroll
-        for (int k = 0; k < kCumPer / 2; ++k) {
-            const ulonglong2 q = s2[k];
-            r.x[2 * k] = q.x;
-            r.x[2 * k + 1] = q.y;
-        }
+        load_vec8(src, r.x);
     } else {
 #pragma unroll
-        for (int k = 0; k < kCumPer; ++k) r.x[k] = base + k < p.n ? dev_load(p.c, base + k) : 0ull;
+        for (int k = 0; k < kTilePer; ++k) r.x[k] = base + k < p.n ? dev_load(p.c, base + k) : 0ull;
     }
 #pragma unroll
-    for (int k = 0; k < kCumPer; ++k)
+    for (int k = 0; k < kTilePer; ++k)
         if (base + k < p.n && dev_valid(p.c, base + k)) r.vm |= 1u << k;
     if constexpr (SEG) {
         // base is a multiple of 8: the thread's start bits are one byte of the bitmap
@@ -272,9 +223,9 @@ __device__ __forceinline__ St cum_elem(const CumParams& p, uint64_t b, bool vali
 template <int K>
 __device__ __forceinline__ void cum_fold(const CumParams& p, const CumRows& r, int bottom, bool& f, St& run) {
 #pragma unroll
-    for (int k = 0; k < kCumPer; ++k) {
+    for (int k = 0; k < kTilePer; ++k) {
         const St e = cum_elem<K>(p, r.x[k], (r.vm >> k) & 1u, bottom);
-        seg_comb<K, false>(f, run, (r.sb >> k) & 1u, e);
+        seg_comb<CumOp<K, false>>(f, run, (r.sb >> k) & 1u, e);
     }
 }
 
@@ -302,26 +253,26 @@ __device__ __forceinline__ St st_words(const St& l) {
 }
 
 template <int K, bool SEG>
-__global__ __launch_bounds__(kCumThreads) void cum_reduce_kernel(CumParams p) {
-    __shared__ St wv[kCumThreads / 64];
-    __shared__ uint32_t wf[kCumThreads / 64];
-    __shared__ int slo[kCumThreads / 64], shi[kCumThreads / 64];
+__global__ __launch_bounds__(kTileThreads) void cum_reduce_kernel(CumParams p) {
+    __shared__ St wv[kTileThreads / 64];
+    __shared__ uint32_t wf[kTileThreads / 64];
+    __shared__ int slo[kTileThreads / 64], shi[kTileThreads / 64];
     const int64_t tile = blockIdx.x;
     // the tile's running total over its blocks (f64 sums: 192 bits on the
     // bottom emin - 1075, emin the smallest exponent of the blocks so far)
     bool rf = false;
     St rv = st_id();
     int emin = 0x7FF, emax = 0;
-    for (int j = 0; j < kCumBlocks; ++j) {
-        const int64_t first = tile * kCumTile + (int64_t)j * kCumBlock;
+    for (int j = 0; j < kTileBlocks; ++j) {
+        const int64_t first = tile * kTileRows + (int64_t)j * kTileBlock;
         if (first >= p.n) break;
-        const int64_t base = first + (int64_t)threadIdx.x * kCumPer;
+        const int64_t base = first + (int64_t)threadIdx.x * kTilePer;
         CumRows r;
         cum_load<SEG>(p, base, r);
         int bmin = 0x7FF, bmax = 0;
         if constexpr (K == CK_SUMF) {
 #pragma unroll
-            for (int k = 0; k < kCumPer; ++k) {
+            for (int k = 0; k < kTilePer; ++k) {
                 const int ex = ((r.vm >> k) & 1u) ? cum_exponent(r.x[k]) : -1;
                 if (ex > 0) {
                     bmin = min(bmin, ex);
@@ -335,7 +286,7 @@ __global__ __launch_bounds__(kCumThreads) void cum_reduce_kernel(CumParams p) {
         cum_fold<K>(p, r, bmin - 1075, f, run);
         bool ef, tf;
         St ev, tv;
-        block_seg_scan<K, false>(f, run, wv, wf, ef, ev, tf, tv);
+        block_seg_scan<CumOp<K, false>>(f, run, wv, wf, ef, ev, tf, tv);
         St tw = st_words<K>(tv);
         if constexpr (K == CK_SUMF) {
             // (shifts past the span belong to a refused column: its sums are not used)
@@ -346,7 +297,7 @@ __global__ __launch_bounds__(kCumThreads) void cum_reduce_kernel(CumParams p) {
                 shl192(tw.a, tw.b, tw.c, min(bmin - emin, kCumSpan));
             }
         }
-        seg_comb<K, true>(rf, rv, tf, tw);
+        seg_comb<CumOp<K, true>>(rf, rv, tf, tw);
     }
     if (threadIdx.x == 0) {
         p.w0[tile] = rv.a;
@@ -378,13 +329,12 @@ __device__ __forceinline__ St cum_summary(const CumParams& p, int64_t t, int emi
 }
 
 template <int K>
-__global__ __launch_bounds__(kCumTotalsThreads) void cum_totals_kernel(CumParams p) {
-    __shared__ St wv[kCumTotalsThreads / 64];
-    __shared__ uint32_t wf[kCumTotalsThreads / 64];
-    __shared__ int slo[kCumTotalsThreads / 64], shi[kCumTotalsThreads / 64];
-    const int64_t per = (p.tiles + kCumTotalsThreads - 1) / kCumTotalsThreads;
-    const int64_t lo = std::min<int64_t>((int64_t)threadIdx.x * per, p.tiles);
-    const int64_t hi = std::min<int64_t>(lo + per, p.tiles);
+__global__ __launch_bounds__(kTotalsThreads) void cum_totals_kernel(CumParams p) {
+    __shared__ St wv[kTotalsThreads / 64];
+    __shared__ uint32_t wf[kTotalsThreads / 64];
+    __shared__ int slo[kTotalsThreads / 64], shi[kTotalsThreads / 64];
+    int64_t lo, hi;
+    totals_span(p.tiles, lo, hi);
     int emin = 0x7FF, emax = 0;
     if constexpr (K == CK_SUMF) {
         for (int64_t t = lo; t < hi; ++t) {
@@ -404,11 +354,11 @@ __global__ __launch_bounds__(kCumTotalsThreads) void cum_totals_kernel(CumParams
     for (int64_t t = lo; t < hi; ++t) {
         bool sf;
         const St s = cum_summary<K>(p, t, emin, sf);
-        seg_comb<K, true>(f, run, sf, s);
+        seg_comb<CumOp<K, true>>(f, run, sf, s);
     }
     bool ef, tf;
     St ev, tv;
-    block_seg_scan<K, true>(f, run, wv, wf, ef, ev, tf, tv);
+    block_seg_scan<CumOp<K, true>>(f, run, wv, wf, ef, ev, tf, tv);
     // the carry of tile t: the running value before it
     for (int64_t t = lo; t < hi; ++t) {
         bool sf;
@@ -419,14 +369,14 @@ __global__ __launch_bounds__(kCumTotalsThreads) void cum_totals_kernel(CumParams
             p.w2[t] = ev.c;
             p.meta[t] = (uint64_t)ev.f << 1;
         }
-        seg_comb<K, true>(ef, ev, sf, s);
+        seg_comb<CumOp<K, true>>(ef, ev, sf, s);
     }
 }
 
 template <int K, bool SEG>
-__global__ __launch_bounds__(kCumThreads) void cum_apply_kernel(CumParams p) {
-    __shared__ St wv[kCumThreads / 64];
-    __shared__ uint32_t wf[kCumThreads / 64];
+__global__ __launch_bounds__(kTileThreads) void cum_apply_kernel(CumParams p) {
+    __shared__ St wv[kTileThreads / 64];
+    __shared__ uint32_t wf[kTileThreads / 64];
     const int64_t tile = blockIdx.x;
     int bottom = 0;
     if constexpr (K == CK_SUMF) bottom = p.info[1] - 1075;
@@ -440,10 +390,10 @@ __global__ __launch_bounds__(kCumThreads) void cum_apply_kernel(CumParams p) {
         cy.c = p.w2[tile];
         cy.f = (uint32_t)(p.meta[tile] >> 1) & 7u;
     }
-    for (int j = 0; j < kCumBlocks; ++j) {
-        const int64_t first = tile * kCumTile + (int64_t)j * kCumBlock;
+    for (int j = 0; j < kTileBlocks; ++j) {
+        const int64_t first = tile * kTileRows + (int64_t)j * kTileBlock;
         if (first >= p.n) break;
-        const int64_t base = first + (int64_t)threadIdx.x * kCumPer;
+        const int64_t base = first + (int64_t)threadIdx.x * kTilePer;
         CumRows r;
         cum_load<SEG>(p, base, r);
         bool f = false;
@@ -451,19 +401,19 @@ __global__ __launch_bounds__(kCumThreads) void cum_apply_kernel(CumParams p) {
         cum_fold<K>(p, r, bottom, f, run);
         bool seen, tf;
         St ev, tv;
-        block_seg_scan<K, false>(f, run, wv, wf, seen, ev, tf, tv);
+        block_seg_scan<CumOp<K, false>>(f, run, wv, wf, seen, ev, tf, tv);
         // integer kinds fold the carry into the thread's prefix; f64 sums add
         // it (192 bits) to the limb sums of the rows before the first start
         if constexpr (K != CK_SUMF) {
             if (!seen) ev = st_comb<K, false>(cy, ev);
         }
-        uint64_t o[kCumPer];
+        uint64_t o[kTilePer];
         uint32_t ovm = 0u;
 #pragma unroll
-        for (int k = 0; k < kCumPer; ++k) {
+        for (int k = 0; k < kTilePer; ++k) {
             const bool valid = (r.vm >> k) & 1u;
             const St e = cum_elem<K>(p, r.x[k], valid, bottom);
-            seg_comb<K, false>(seen, ev, (r.sb >> k) & 1u, e);
+            seg_comb<CumOp<K, false>>(seen, ev, (r.sb >> k) & 1u, e);
             uint64_t v = 0ull;
             if constexpr (K == CK_COUNT) {
                 v = ev.a;
@@ -488,38 +438,28 @@ __global__ __launch_bounds__(kCumThreads) void cum_apply_kernel(CumParams p) {
             }
             o[k] = v;
         }
-        seg_comb<K, true>(cf, cy, tf, st_words<K>(tv));  // the carry of the next block
+        seg_comb<CumOp<K, true>>(cf, cy, tf, st_words<K>(tv));  // the carry of the next block
         if (base >= p.n) {  // the rest of the last validity word
             if (p.out_valid != nullptr && base < (p.n + 63) / 64 * 64) p.out_valid[base >> 3] = 0;
             continue;
         }
-        if (dtype_bytes(p.out_dtype) == 8 && base + kCumPer <= p.n) {
+        if (dtype_bytes(p.out_dtype) == 8 && base + kTilePer <= p.n) {
             ulonglong2* d2 = (ulonglong2*)((uint64_t*)p.out + base);  // an owned buffer, base even: 16-byte aligned
 #pragma unroll
-            for (int k = 0; k < kCumPer / 2; ++k) d2[k] = make_ulonglong2(o[2 * k], o[2 * k + 1]);
-        } else if (dtype_bytes(p.out_dtype) == 4 && base + kCumPer <= p.n) {
+            for (int k = 0; k < kTilePer / 2; ++k) d2[k] = make_ulonglong2(o[2 * k], o[2 * k + 1]);
+        } else if (dtype_bytes(p.out_dtype) == 4 && base + kTilePer <= p.n) {
             uint4* d4 = (uint4*)((uint32_t*)p.out + base);
             d4[0] = make_uint4((uint32_t)o[0], (uint32_t)o[1], (uint32_t)o[2], (uint32_t)o[3]);
             d4[1] = make_uint4((uint32_t)o[4], (uint32_t)o[5], (uint32_t)o[6], (uint32_t)o[7]);
         } else {
 #pragma unroll
-            for (int k = 0; k < kCumPer; ++k)
+            for (int k = 0; k < kTilePer; ++k)
                 if (base + k < p.n) {
                     if (dtype_bytes(p.out_dtype) == 8) ((uint64_t*)p.out)[base + k] = o[k];
                     else ((uint32_t*)p.out)[base + k] = (uint32_t)o[k];
                 }
         }
         if (p.out_valid != nullptr) p.out_valid[base >> 3] = (uint8_t)ovm;  // rows past the column: zero bits
-    }
-}
-
-// Bits [off, off + n) of a Boolean column as words from bit 0.
-__global__ __launch_bounds__(256) void cum_seg_repack_kernel(DevCol c, int64_t n, uint64_t* __restrict__ out) {
-    const int64_t words = (n + 63) / 64;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < words * 64;
-         r += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t m = __ballot(r < n && dev_load(c, r) != 0);
-        if ((threadIdx.x & 63) == 0) out[r >> 6] = m;
     }
 }
 
@@ -537,19 +477,11 @@ struct LagParams {
     uint64_t* out_valid;
 };
 
-__device__ __forceinline__ uint64_t lag_seg_word(const uint64_t* seg, int64_t nbytes, int64_t wi) {
-    if ((wi + 1) * 8 <= nbytes) return seg[wi];
-    uint64_t v = 0;  // the last, partial word byte by byte (a caller's bitmap need not be padded)
-    const uint8_t* b = (const uint8_t*)seg;
-    for (int64_t j = wi * 8; j < nbytes; ++j) v |= (uint64_t)b[j] << (8 * (j - wi * 8));
-    return v;
-}
-
 // Is a segment start among rows (lo, hi]?  (0 <= lo <= hi < n.)
 __device__ __forceinline__ bool lag_seg_any(const uint64_t* seg, int64_t nbytes, int64_t lo, int64_t hi) {
     const int64_t q = lo + 1;
     for (int64_t wi = q >> 6; (wi << 6) <= hi; ++wi) {
-        uint64_t m = lag_seg_word(seg, nbytes, wi);
+        uint64_t m = seg_word(seg, nbytes, wi);
         if ((wi << 6) < q) m &= ~0ull << (int)(q & 63);
         if (hi - (wi << 6) < 63) m &= ~0ull >> (63 - (int)(hi - (wi << 6)));
         if (m) return true;
@@ -604,50 +536,22 @@ __global__ __launch_bounds__(256) void lag_kernel(LagParams p) {
     }
 }
 
-// Checks of a segment-start column against its values; the bitmap as 8-byte
-// words from bit 0: the column's own buffer where it is laid out so (as
-// plgpu_segment_starts writes it), else a copy in `own`.
-int seg_check(const plgpu_column* values, const plgpu_column* seg_starts) {
-    if (seg_starts->dtype != PLGPU_BOOL) return fail(PLGPU_ERR_SCHEMA, "segment starts must be a Boolean column");
-    if (seg_starts->validity != nullptr) return fail(PLGPU_ERR_SCHEMA, "segment starts must not be nullable");
-    if (seg_starts->length != values->length)
-        return fail(PLGPU_ERR_SHAPE, "segment starts and values must have equal lengths");
-    return PLGPU_OK;
-}
-
-int seg_words(const plgpu_column* seg_starts, int64_t n, DevBuf<uint64_t>& own, const uint64_t** seg, hipStream_t s) {
-    const uintptr_t at = (uintptr_t)seg_starts->values + (uintptr_t)(seg_starts->offset / 8);
-    if (seg_starts->offset % 8 == 0 && at % 8 == 0) {
-        *seg = (const uint64_t*)at;
-        return PLGPU_OK;
-    }
-    const int64_t words = (n + 63) / 64;
-    const int rc = own.alloc((size_t)words * 8, s);
-    if (rc) return rc;
-    cum_seg_repack_kernel<<<(unsigned)std::min<int64_t>((words * 64 + 255) / 256, 256 * 64), 256, 0, s>>>(
-        dev_col(*seg_starts), n, own);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "segment starts");
-    *seg = own;
-    return PLGPU_OK;
-}
-
 template <int K>
 void cum_launch(const CumParams& p, hipStream_t s) {
     const unsigned g = (unsigned)p.tiles;
     {
         KtScope kt("cum_reduce_kernel", s);
-        if (p.seg) cum_reduce_kernel<K, true><<<g, kCumThreads, 0, s>>>(p);
-        else cum_reduce_kernel<K, false><<<g, kCumThreads, 0, s>>>(p);
+        if (p.seg) cum_reduce_kernel<K, true><<<g, kTileThreads, 0, s>>>(p);
+        else cum_reduce_kernel<K, false><<<g, kTileThreads, 0, s>>>(p);
     }
     {
         KtScope kt("cum_totals_kernel", s);
-        cum_totals_kernel<K><<<1, kCumTotalsThreads, 0, s>>>(p);
+        cum_totals_kernel<K><<<1, kTotalsThreads, 0, s>>>(p);
     }
     {
         KtScope kt("cum_apply_kernel", s);
-        if (p.seg) cum_apply_kernel<K, true><<<g, kCumThreads, 0, s>>>(p);
-        else cum_apply_kernel<K, false><<<g, kCumThreads, 0, s>>>(p);
+        if (p.seg) cum_apply_kernel<K, true><<<g, kTileThreads, 0, s>>>(p);
+        else cum_apply_kernel<K, false><<<g, kTileThreads, 0, s>>>(p);
     }
 }
 
@@ -669,7 +573,7 @@ PLGPU_API int plgpu_cumulative(const plgpu_column* values, const plgpu_column* s
         return fail(PLGPU_ERR_SCHEMA, "cumulative input must be Float64 / Int64 / Int32 / UInt64");
     }
     if (seg_starts != nullptr) {
-        const int rc = seg_check(values, seg_starts);
+        const int rc = seg_check(values, seg_starts, PLGPU_ERR_SCHEMA, PLGPU_ERR_SHAPE);
         if (rc) return rc;
     }
     const int64_t n = values->length;
@@ -689,7 +593,7 @@ PLGPU_API int plgpu_cumulative(const plgpu_column* values, const plgpu_column* s
     p.out_dtype = out->dtype;
     p.out = (void*)out->values;
     p.out_valid = (uint8_t*)out->validity;
-    p.tiles = (n + kCumTile - 1) / kCumTile;
+    p.tiles = (n + kTileRows - 1) / kTileRows;
     const bool sumf = kind == PLGPU_CUM_SUM && dt == PLGPU_F64;
     if (!rc) rc = words.alloc((size_t)p.tiles * 8 * 4, s);
     if (!rc) rc = info.alloc(4 * sizeof(int32_t), s);
@@ -731,7 +635,7 @@ PLGPU_API int plgpu_lag(const plgpu_column* values, const plgpu_column* seg_star
     if (kind == PLGPU_LAG_DIFF && (values->dtype == PLGPU_U32 || values->dtype == PLGPU_U64))
         return fail(PLGPU_ERR_SCHEMA, "diff of an unsigned column: cast it to Int64 first");
     if (seg_starts != nullptr) {
-        const int rc = seg_check(values, seg_starts);
+        const int rc = seg_check(values, seg_starts, PLGPU_ERR_SCHEMA, PLGPU_ERR_SHAPE);
         if (rc) return rc;
     }
     const int64_t len = values->length;

@@ -26,8 +26,8 @@
 // the map, and the segmented non-null count travels there too (min_samples).
 //
 // Three launches, none of which waits on another workgroup.
-// ewm_reduce_kernel: one workgroup per tile of kEwmTile rows, taken as
-// kEwmBlocks block scans of kEwmBlock rows, leaves the tile's map (after its
+// ewm_reduce_kernel: one workgroup per tile of kTileRows rows, taken as
+// kTileBlocks block scans of kTileBlock rows, leaves the tile's map (after its
 // last start, or of all its rows) and, without adjust, its bitmap codes and
 // the one row whose map depends on earlier tiles (the tile's first non-null
 // row, when no start precedes it).  ewm_totals_kernel: one workgroup scans the
@@ -41,22 +41,14 @@
 #include <cstring>
 #include <type_traits>
 
-#include "bitmap_scan.hpp"
 #include "plgpu_internal.hpp"
+#include "seg_scan.hpp"
 
 namespace plgpu {
 namespace {
 
-constexpr int kEwmThreads = 256;
-constexpr int kEwmPer = 8;                        // consecutive rows per thread
-constexpr int kEwmBlock = kEwmThreads * kEwmPer;  // rows of one workgroup scan
-constexpr int kEwmBlocks = 8;                     // scans a workgroup runs one after the other
-constexpr int kEwmTile = kEwmBlock * kEwmBlocks;  // rows per workgroup: kCumTile (cumulative.hip)
-constexpr int kEwmWords = kEwmTile / 64;          // bitmap words of a tile: one per thread
-constexpr int kEwmTotalsThreads = 1024;
 constexpr int kEwmPowLoop = 8;                    // (1 - alpha)^k by k products up to here, pow() above
 constexpr uint32_t kEwmNf = 1u;                   // a non-finite value was seen
-static_assert(kEwmWords == kEwmThreads, "one bitmap word per thread");
 
 struct EwmParams {
     const void* values;    // the slice's first element is values[voff]
@@ -130,53 +122,14 @@ __device__ __forceinline__ Em em_shfl_up(const Em& x, int off) {
     return y;
 }
 
-// (flag, map) (+) (flag, map) of the segmented scan: a start replaces.
+// The operator of the segmented scan (seg_scan.hpp).
 template <bool ADJ>
-__device__ __forceinline__ void em_seg_comb(bool& lf, Em& l, bool rf, const Em& r) {
-    l = rf ? r : em_comb<ADJ>(l, r);
-    lf = lf || rf;
-}
-
-// Segmented scan of one (flag, map) per thread over the workgroup: the
-// exclusive prefix of this thread in (ef, ev), the workgroup's total in
-// (tf, tv).  wv / wf: one slot per wave.
-template <bool ADJ>
-__device__ __forceinline__ void em_block_scan(bool f, const Em& v, Em* wv, uint32_t* wf, bool& ef, Em& ev, bool& tf,
-                                              Em& tv) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    Em x = v;
-    uint32_t xf = f ? 1u : 0u;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const Em y = em_shfl_up<ADJ>(x, off);
-        const uint32_t yf = __shfl_up(xf, off, 64);
-        if (lane >= off) {
-            if (!xf) x = em_comb<ADJ>(y, x);
-            xf |= yf;
-        }
-    }
-    if (lane == 63) {
-        wv[wid] = x;
-        wf[wid] = xf;
-    }
-    Em px = em_shfl_up<ADJ>(x, 1);
-    uint32_t pf = __shfl_up(xf, 1, 64);
-    if (lane == 0) {
-        px = em_id<ADJ>();
-        pf = 0u;
-    }
-    __syncthreads();
-    ef = false;
-    ev = em_id<ADJ>();
-    tf = false;
-    tv = em_id<ADJ>();
-    for (int w = 0; w < nw; ++w) {
-        if (w < wid) em_seg_comb<ADJ>(ef, ev, wf[w] != 0u, wv[w]);
-        em_seg_comb<ADJ>(tf, tv, wf[w] != 0u, wv[w]);
-    }
-    em_seg_comb<ADJ>(ef, ev, pf != 0u, px);
-    __syncthreads();
-}
+struct EmOp {
+    using T = Em;
+    static __device__ __forceinline__ Em id() { return em_id<ADJ>(); }
+    static __device__ __forceinline__ Em comb(const Em& l, const Em& r) { return em_comb<ADJ>(l, r); }
+    static __device__ __forceinline__ Em shfl_up(const Em& x, int off) { return em_shfl_up<ADJ>(x, off); }
+};
 
 // F of a non-null row that follows `gap` nulls after the previous non-null
 // row: the reference's weight there is 1 * d * ... * d, gap + 1 factors.
@@ -204,7 +157,7 @@ __device__ __forceinline__ void ewm_tile_words(const EwmParams& p, int64_t tile,
                                                uint64_t* sV, uint64_t* sS, uint64_t* sJ, uint64_t* sT, uint64_t* wa,
                                                uint64_t* wb, uint64_t& tj, uint64_t& ts) {
     const int t = threadIdx.x;
-    const int64_t r0 = (tile * kEwmWords + t) * 64;
+    const int64_t r0 = (tile * kTileWords + t) * 64;
     uint64_t V = 0ull, S = 0ull;
     if (r0 < p.n) {
         const uint64_t in = fill_lowmask(p.n - r0);
@@ -227,10 +180,10 @@ __device__ __forceinline__ void ewm_tile_words(const EwmParams& p, int64_t tile,
     __syncthreads();
 }
 
-// The thread's kEwmPer rows of one block scan.
+// The thread's kTilePer rows of one block scan.
 struct EwmRows {
-    double x[kEwmPer];
-    double F[kEwmPer];  // no adjust: F of a non-null row (0: the row left to the totals launch)
+    double x[kTilePer];
+    double F[kTilePer];  // no adjust: F of a non-null row (0: the row left to the totals launch)
     uint32_t vb;        // bit k: row k is inside the column and not null
     uint32_t sb;        // bit k: row k starts a segment
     uint32_t nf;        // bit k: row k is non-null and not finite
@@ -245,35 +198,29 @@ __device__ __forceinline__ void ewm_load(const EwmParams& p, int64_t tile, int b
                                          uint64_t* pcode, double* px) {
     using T = typename std::conditional<F32, float, double>::type;
     const int t = threadIdx.x;
-    const int64_t base = tile * kEwmTile + (int64_t)blk * kEwmBlock + (int64_t)t * kEwmPer;
-    const int wi = blk * (kEwmBlock / 64) + (t >> 3);
-    const int b0 = (t & 7) * kEwmPer;  // the thread's rows are bits b0 .. b0 + 7 of the word
+    const int64_t base = tile * kTileRows + (int64_t)blk * kTileBlock + (int64_t)t * kTilePer;
+    const int wi = blk * (kTileBlock / 64) + (t >> 3);
+    const int b0 = (t & 7) * kTilePer;  // the thread's rows are bits b0 .. b0 + 7 of the word
     const uint64_t V = sV[wi], S = sS[wi];
     r.vb = (uint32_t)(V >> b0) & 0xFFu;
     r.sb = (uint32_t)(S >> b0) & 0xFFu;
     r.nf = 0u;
     const T* src = (const T*)p.values + p.voff;
-    if (base + kEwmPer <= p.n && ((uintptr_t)src & 15u) == 0) {
+    if (base + kTilePer <= p.n && ((uintptr_t)src & 15u) == 0) {
         if constexpr (F32) {
-            const float4* s4 = (const float4*)(src + base);
-            const float4 q0 = s4[0], q1 = s4[1];
-            r.x[0] = q0.x; r.x[1] = q0.y; r.x[2] = q0.z; r.x[3] = q0.w;
-            r.x[4] = q1.x; r.x[5] = q1.y; r.x[6] = q1.z; r.x[7] = q1.w;
-        } else {
-            const double2* s2 = (const double2*)(src + base);
+            float x[kTilePer];
+            load_vec8(src + base, x);
 #pragma unroll
-            for (int k = 0; k < kEwmPer / 2; ++k) {
-                const double2 q = s2[k];
-                r.x[2 * k] = q.x;
-                r.x[2 * k + 1] = q.y;
-            }
+            for (int k = 0; k < kTilePer; ++k) r.x[k] = x[k];
+        } else {
+            load_vec8(src + base, r.x);
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < kEwmPer; ++k) r.x[k] = base + k < p.n ? (double)src[base + k] : 0.0;
+        for (int k = 0; k < kTilePer; ++k) r.x[k] = base + k < p.n ? (double)src[base + k] : 0.0;
     }
 #pragma unroll
-    for (int k = 0; k < kEwmPer; ++k) {
+    for (int k = 0; k < kTilePer; ++k) {
         if (!((r.vb >> k) & 1u)) r.x[k] = 0.0;  // a null row's bytes are not a value
         else if (!ewm_finite(r.x[k])) r.nf |= 1u << k;
     }
@@ -281,11 +228,11 @@ __device__ __forceinline__ void ewm_load(const EwmParams& p, int64_t tile, int b
         // the codes that enter the thread's rows: the word's bits before them, else the word's own entry codes
         const uint64_t before = (1ull << b0) - 1ull;
         const uint64_t mj = V & before, ms = S & before;
-        const int64_t r0 = (tile * kEwmWords + wi) * 64;
+        const int64_t r0 = (tile * kTileWords + wi) * 64;
         uint64_t jc = mj ? fill_word_code<false>(mj, r0) : sJ[wi];
         uint64_t sc = ms ? fill_word_code<false>(ms, r0) : sT[wi];
 #pragma unroll
-        for (int k = 0; k < kEwmPer; ++k) {
+        for (int k = 0; k < kTilePer; ++k) {
             const uint64_t ic = fill_row_code<false>(base + k);
             if ((r.sb >> k) & 1u) sc = ic;
             r.F[k] = 0.0;
@@ -331,15 +278,15 @@ __device__ __forceinline__ Em ewm_elem(const EwmParams& p, const EwmRows& r, int
 template <bool ADJ>
 __device__ __forceinline__ void ewm_fold(const EwmParams& p, const EwmRows& r, bool& f, Em& run) {
 #pragma unroll
-    for (int k = 0; k < kEwmPer; ++k) em_seg_comb<ADJ>(f, run, (r.sb >> k) & 1u, ewm_elem<ADJ>(p, r, k));
+    for (int k = 0; k < kTilePer; ++k) seg_comb<EmOp<ADJ>>(f, run, (r.sb >> k) & 1u, ewm_elem<ADJ>(p, r, k));
 }
 
 template <bool ADJ, bool F32>
-__global__ __launch_bounds__(kEwmThreads) void ewm_reduce_kernel(EwmParams p) {
-    __shared__ uint64_t sV[kEwmWords], sS[kEwmWords], sJ[kEwmWords], sT[kEwmWords];
-    __shared__ uint64_t wa[kEwmThreads / 64], wb[kEwmThreads / 64];
-    __shared__ Em wv[kEwmThreads / 64];
-    __shared__ uint32_t wf[kEwmThreads / 64];
+__global__ __launch_bounds__(kTileThreads) void ewm_reduce_kernel(EwmParams p) {
+    __shared__ uint64_t sV[kTileWords], sS[kTileWords], sJ[kTileWords], sT[kTileWords];
+    __shared__ uint64_t wa[kTileThreads / 64], wb[kTileThreads / 64];
+    __shared__ Em wv[kTileThreads / 64];
+    __shared__ uint32_t wf[kTileThreads / 64];
     __shared__ uint64_t pcode;
     __shared__ double px;
     const int64_t tile = blockIdx.x;
@@ -351,8 +298,8 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_reduce_kernel(EwmParams p) {
     ewm_tile_words<ADJ>(p, tile, p.seg != nullptr, 0ull, 0ull, sV, sS, sJ, sT, wa, wb, tj, ts);
     bool rf = false;
     Em rv = em_id<ADJ>();
-    for (int j = 0; j < kEwmBlocks; ++j) {
-        if (tile * kEwmTile + (int64_t)j * kEwmBlock >= p.n) break;
+    for (int j = 0; j < kTileBlocks; ++j) {
+        if (tile * kTileRows + (int64_t)j * kTileBlock >= p.n) break;
         EwmRows r;
         ewm_load<ADJ, F32, true>(p, tile, j, sV, sS, sJ, sT, r, &pcode, &px);
         bool f = false;
@@ -360,8 +307,8 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_reduce_kernel(EwmParams p) {
         ewm_fold<ADJ>(p, r, f, run);
         bool ef, tf;
         Em ev, tv;
-        em_block_scan<ADJ>(f, run, wv, wf, ef, ev, tf, tv);
-        em_seg_comb<ADJ>(rf, rv, tf, tv);
+        block_seg_scan<EmOp<ADJ>>(f, run, wv, wf, ef, ev, tf, tv);
+        seg_comb<EmOp<ADJ>>(rf, rv, tf, tv);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -376,7 +323,7 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_reduce_kernel(EwmParams p) {
         }
     }
     if constexpr (!ADJ) {
-        if (threadIdx.x == kEwmThreads - 1) {
+        if (threadIdx.x == kTileThreads - 1) {
             p.cj[tile] = tj;
             p.cs[tile] = ts;
         }
@@ -390,13 +337,12 @@ __device__ __forceinline__ Em ewm_summary(const EwmParams& p, int64_t t, bool& f
 }
 
 template <bool ADJ>
-__global__ __launch_bounds__(kEwmTotalsThreads) void ewm_totals_kernel(EwmParams p) {
-    __shared__ uint64_t wa[kEwmTotalsThreads / 64], wb[kEwmTotalsThreads / 64];
-    __shared__ Em wv[kEwmTotalsThreads / 64];
-    __shared__ uint32_t wf[kEwmTotalsThreads / 64];
-    const int64_t per = (p.tiles + kEwmTotalsThreads - 1) / kEwmTotalsThreads;
-    const int64_t lo = std::min<int64_t>((int64_t)threadIdx.x * per, p.tiles);
-    const int64_t hi = std::min<int64_t>(lo + per, p.tiles);
+__global__ __launch_bounds__(kTotalsThreads) void ewm_totals_kernel(EwmParams p) {
+    __shared__ uint64_t wa[kTotalsThreads / 64], wb[kTotalsThreads / 64];
+    __shared__ Em wv[kTotalsThreads / 64];
+    __shared__ uint32_t wf[kTotalsThreads / 64];
+    int64_t lo, hi;
+    totals_span(p.tiles, lo, hi);
     uint64_t a = 0ull, b = 0ull;
     if constexpr (!ADJ) {
         for (int64_t t = lo; t < hi; ++t) {
@@ -426,11 +372,11 @@ __global__ __launch_bounds__(kEwmTotalsThreads) void ewm_totals_kernel(EwmParams
             a = fill_max(a, va);
             b = fill_max(b, vb);
         }
-        em_seg_comb<ADJ>(f, run, sf, s);
+        seg_comb<EmOp<ADJ>>(f, run, sf, s);
     }
     bool ef, tf;
     Em ev, tv;
-    em_block_scan<ADJ>(f, run, wv, wf, ef, ev, tf, tv);
+    block_seg_scan<EmOp<ADJ>>(f, run, wv, wf, ef, ev, tf, tv);
     // the carry of tile t: the running map before it
     for (int64_t t = lo; t < hi; ++t) {
         bool sf;
@@ -440,17 +386,17 @@ __global__ __launch_bounds__(kEwmTotalsThreads) void ewm_totals_kernel(EwmParams
         p.sr[t] = ev.r;
         p.scnt[t] = ev.cnt;
         p.smeta[t] = (uint64_t)ev.fl << 1;
-        em_seg_comb<ADJ>(ef, ev, sf, s);
+        seg_comb<EmOp<ADJ>>(ef, ev, sf, s);
     }
 }
 
 template <bool ADJ, bool F32, bool SEG>
-__global__ __launch_bounds__(kEwmThreads) void ewm_apply_kernel(EwmParams p) {
+__global__ __launch_bounds__(kTileThreads) void ewm_apply_kernel(EwmParams p) {
     using T = typename std::conditional<F32, float, double>::type;
-    __shared__ uint64_t sV[kEwmWords], sS[kEwmWords], sJ[kEwmWords], sT[kEwmWords];
-    __shared__ uint64_t wa[kEwmThreads / 64], wb[kEwmThreads / 64];
-    __shared__ Em wv[kEwmThreads / 64];
-    __shared__ uint32_t wf[kEwmThreads / 64];
+    __shared__ uint64_t sV[kTileWords], sS[kTileWords], sJ[kTileWords], sT[kTileWords];
+    __shared__ uint64_t wa[kTileThreads / 64], wb[kTileThreads / 64];
+    __shared__ Em wv[kTileThreads / 64];
+    __shared__ uint32_t wf[kTileThreads / 64];
     const int64_t tile = blockIdx.x;
     uint64_t tj, ts;
     ewm_tile_words<ADJ>(p, tile, SEG, ADJ ? 0ull : p.cj[tile], ADJ ? 0ull : p.cs[tile], sV, sS, sJ, sT, wa, wb, tj, ts);
@@ -459,10 +405,10 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_apply_kernel(EwmParams p) {
     Em cy = ewm_summary(p, tile, sf0);
     T* dst = (T*)p.out;
     const int64_t padded = (p.n + 63) / 64 * 64;
-    for (int j = 0; j < kEwmBlocks; ++j) {
-        const int64_t first = tile * kEwmTile + (int64_t)j * kEwmBlock;
+    for (int j = 0; j < kTileBlocks; ++j) {
+        const int64_t first = tile * kTileRows + (int64_t)j * kTileBlock;
         if (first >= p.n) break;
-        const int64_t base = first + (int64_t)threadIdx.x * kEwmPer;
+        const int64_t base = first + (int64_t)threadIdx.x * kTilePer;
         EwmRows r;
         ewm_load<ADJ, F32, false>(p, tile, j, sV, sS, sJ, sT, r, nullptr, nullptr);
         bool f = false;
@@ -470,15 +416,15 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_apply_kernel(EwmParams p) {
         ewm_fold<ADJ>(p, r, f, run);
         bool seen, tf;
         Em ev, tv;
-        em_block_scan<ADJ>(f, run, wv, wf, seen, ev, tf, tv);
+        block_seg_scan<EmOp<ADJ>>(f, run, wv, wf, seen, ev, tf, tv);
         if (!seen) ev = em_comb<ADJ>(cy, ev);
-        T o[kEwmPer];
+        T o[kTilePer];
         uint32_t ob = 0u;
 #pragma unroll
-        for (int k = 0; k < kEwmPer; ++k) {
+        for (int k = 0; k < kTilePer; ++k) {
             const bool valid = (r.vb >> k) & 1u, start = (r.sb >> k) & 1u;
             const bool nf_before = !start && (ev.fl & kEwmNf) != 0u;
-            em_seg_comb<ADJ>(seen, ev, start, ewm_elem<ADJ>(p, r, k));
+            seg_comb<EmOp<ADJ>>(seen, ev, start, ewm_elem<ADJ>(p, r, k));
             double d = 0.0;
             if (valid) {
                 // the first non-finite value of a segment comes out as itself, every later row as
@@ -490,12 +436,12 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_apply_kernel(EwmParams p) {
             }
             o[k] = (T)d;  // Float32: computed in f64, rounded once here
         }
-        em_seg_comb<ADJ>(cf, cy, tf, tv);  // the carry of the next block
+        seg_comb<EmOp<ADJ>>(cf, cy, tf, tv);  // the carry of the next block
         if (base >= p.n) {  // the rest of the last validity word
             if (base < padded) p.out_valid[base >> 3] = 0;
             continue;
         }
-        if (base + kEwmPer <= p.n) {  // an owned buffer, base a multiple of 8: 16-byte aligned
+        if (base + kTilePer <= p.n) {  // an owned buffer, base a multiple of 8: 16-byte aligned
             if constexpr (F32) {
                 float4* d4 = (float4*)(dst + base);
                 d4[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -503,11 +449,11 @@ __global__ __launch_bounds__(kEwmThreads) void ewm_apply_kernel(EwmParams p) {
             } else {
                 double2* d2 = (double2*)(dst + base);
 #pragma unroll
-                for (int k = 0; k < kEwmPer / 2; ++k) d2[k] = make_double2(o[2 * k], o[2 * k + 1]);
+                for (int k = 0; k < kTilePer / 2; ++k) d2[k] = make_double2(o[2 * k], o[2 * k + 1]);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < kEwmPer; ++k)
+            for (int k = 0; k < kTilePer; ++k)
                 if (base + k < p.n) dst[base + k] = o[k];
         }
         p.out_valid[base >> 3] = (uint8_t)ob;  // rows past the column: zero bits
@@ -519,16 +465,16 @@ void ewm_launch(const EwmParams& p, hipStream_t s) {
     const unsigned g = (unsigned)p.tiles;
     {
         KtScope kt("ewm_reduce_kernel", s);
-        ewm_reduce_kernel<ADJ, F32><<<g, kEwmThreads, 0, s>>>(p);
+        ewm_reduce_kernel<ADJ, F32><<<g, kTileThreads, 0, s>>>(p);
     }
     {
         KtScope kt("ewm_totals_kernel", s);
-        ewm_totals_kernel<ADJ><<<1, kEwmTotalsThreads, 0, s>>>(p);
+        ewm_totals_kernel<ADJ><<<1, kTotalsThreads, 0, s>>>(p);
     }
     {
         KtScope kt("ewm_apply_kernel", s);
-        if (p.seg) ewm_apply_kernel<ADJ, F32, true><<<g, kEwmThreads, 0, s>>>(p);
-        else ewm_apply_kernel<ADJ, F32, false><<<g, kEwmThreads, 0, s>>>(p);
+        if (p.seg) ewm_apply_kernel<ADJ, F32, true><<<g, kTileThreads, 0, s>>>(p);
+        else ewm_apply_kernel<ADJ, F32, false><<<g, kTileThreads, 0, s>>>(p);
     }
 }
 
@@ -545,10 +491,8 @@ PLGPU_API int plgpu_ewm_mean(const plgpu_column* values, const plgpu_column* seg
     if (!(alpha > 0.0 && alpha <= 1.0)) return fail(PLGPU_ERR_INVALID, "ewm_mean: alpha must lie in (0, 1]");
     if (min_samples < 0) return fail(PLGPU_ERR_INVALID, "ewm_mean: min_samples must not be negative");
     if (seg_starts != nullptr) {
-        if (seg_starts->dtype != PLGPU_BOOL || seg_starts->validity != nullptr)
-            return fail(PLGPU_ERR_INVALID, "segment starts must be a null-free Boolean column");
-        if (seg_starts->length != values->length)
-            return fail(PLGPU_ERR_INVALID, "segment starts and values must have equal lengths");
+        const int rc = seg_check(values, seg_starts, PLGPU_ERR_INVALID, PLGPU_ERR_INVALID);
+        if (rc) return rc;
     }
     const int32_t dt = values->dtype;
     if (dt != PLGPU_F32 && dt != PLGPU_F64) return fail(PLGPU_ERR_SCHEMA, "ewm_mean input must be Float32 / Float64");
@@ -577,7 +521,7 @@ PLGPU_API int plgpu_ewm_mean(const plgpu_column* values, const plgpu_column* seg
     p.min_count = (uint64_t)std::max<int64_t>(min_samples, 1);
     p.out = (void*)out->values;
     p.out_valid = (uint8_t*)out->validity;
-    p.tiles = (n + kEwmTile - 1) / kEwmTile;
+    p.tiles = (n + kTileRows - 1) / kTileRows;
     DevBuf<uint64_t> words;
     rc = words.alloc((size_t)p.tiles * 8 * 9, s);
     if (!rc) {

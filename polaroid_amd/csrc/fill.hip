@@ -20,7 +20,7 @@
 //
 // Three launches, none of which waits on another workgroup:
 // fill_reduce_kernel reads the bitmaps alone, one 64-row word per lane, and
-// leaves two codes per tile of kFillTile rows; fill_totals_kernel (one
+// leaves two codes per tile of kTileRows rows; fill_totals_kernel (one
 // workgroup) turns them into every tile's carry, an exclusive running maximum
 // in the direction of the fill; fill_apply_kernel scans the per-word codes of
 // its tile, adds the carry, and streams the values once: a null row that
@@ -33,20 +33,11 @@
 #include <cstring>
 #include <type_traits>
 
-#include "bitmap_scan.hpp"
 #include "plgpu_internal.hpp"
+#include "seg_scan.hpp"
 
 namespace plgpu {
 namespace {
-
-constexpr int kFillThreads = 256;
-constexpr int kFillPer = 8;                          // consecutive rows per thread
-constexpr int kFillBlock = kFillThreads * kFillPer;  // rows of one pass of the workgroup over the values
-constexpr int kFillBlocks = 8;
-constexpr int kFillTile = kFillBlock * kFillBlocks;  // rows per workgroup: kCumTile (cumulative.hip)
-constexpr int kFillWords = kFillTile / 64;           // validity words of a tile: one per thread
-constexpr int kFillTotalsThreads = 1024;
-static_assert(kFillWords == kFillThreads, "one validity word per thread");
 
 struct FillParams {
     const void* values;      // the slice's first element is values[voff]
@@ -82,10 +73,10 @@ __device__ __forceinline__ void fill_words(const FillParams& p, int64_t w, bool 
 }
 
 template <bool REV>
-__global__ __launch_bounds__(kFillThreads) void fill_reduce_kernel(FillParams p) {
-    __shared__ uint64_t wa[kFillThreads / 64], wb[kFillThreads / 64];
+__global__ __launch_bounds__(kTileThreads) void fill_reduce_kernel(FillParams p) {
+    __shared__ uint64_t wa[kTileThreads / 64], wb[kTileThreads / 64];
     const int64_t tile = blockIdx.x;
-    const int64_t w = tile * kFillWords + threadIdx.x;
+    const int64_t w = tile * kTileWords + threadIdx.x;
     uint64_t V, S;
     fill_words<REV>(p, w, p.seg != nullptr, V, S);
     uint64_t a = fill_word_code<REV>(V, w * 64), b = fill_word_code<REV>(S, w * 64);
@@ -100,7 +91,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_reduce_kernel(FillParams p)
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int k = 1; k < kFillThreads / 64; ++k) {
+        for (int k = 1; k < kTileThreads / 64; ++k) {
             a = fill_max(a, wa[k]);
             b = fill_max(b, wb[k]);
         }
@@ -110,12 +101,11 @@ __global__ __launch_bounds__(kFillThreads) void fill_reduce_kernel(FillParams p)
 }
 
 template <bool REV>
-__global__ __launch_bounds__(kFillTotalsThreads) void fill_totals_kernel(FillParams p) {
-    __shared__ uint64_t wa[kFillTotalsThreads / 64], wb[kFillTotalsThreads / 64];
+__global__ __launch_bounds__(kTotalsThreads) void fill_totals_kernel(FillParams p) {
+    __shared__ uint64_t wa[kTotalsThreads / 64], wb[kTotalsThreads / 64];
     // position q of the scan is tile q forward, tile tiles - 1 - q backward
-    const int64_t per = (p.tiles + kFillTotalsThreads - 1) / kFillTotalsThreads;
-    const int64_t lo = std::min<int64_t>((int64_t)threadIdx.x * per, p.tiles);
-    const int64_t hi = std::min<int64_t>(lo + per, p.tiles);
+    int64_t lo, hi;
+    totals_span(p.tiles, lo, hi);
     uint64_t a = 0ull, b = 0ull;
     for (int64_t q = lo; q < hi; ++q) {
         const int64_t t = REV ? p.tiles - 1 - q : q;
@@ -135,16 +125,16 @@ __global__ __launch_bounds__(kFillTotalsThreads) void fill_totals_kernel(FillPar
 }
 
 template <int BYTES, bool REV, bool SEG>
-__global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) {
+__global__ __launch_bounds__(kTileThreads) void fill_apply_kernel(FillParams p) {
     using T = typename std::conditional<BYTES == 8, uint64_t, uint32_t>::type;
-    __shared__ uint64_t sV[kFillWords], sS[kFillWords], sJ[kFillWords], sT[kFillWords];
-    __shared__ uint64_t wa[kFillThreads / 64], wb[kFillThreads / 64];
+    __shared__ uint64_t sV[kTileWords], sS[kTileWords], sJ[kTileWords], sT[kTileWords];
+    __shared__ uint64_t wa[kTileThreads / 64], wb[kTileThreads / 64];
     const int64_t tile = blockIdx.x;
     const int t = threadIdx.x;
     {
         // the codes that enter every word of the tile: thread order is scan order
-        const int wi = REV ? kFillWords - 1 - t : t;
-        const int64_t w = tile * kFillWords + wi;
+        const int wi = REV ? kTileWords - 1 - t : t;
+        const int64_t w = tile * kTileWords + wi;
         uint64_t V, S;
         fill_words<REV>(p, w, SEG, V, S);
         uint64_t a = fill_word_code<REV>(V, w * 64), b = SEG ? fill_word_code<REV>(S, w * 64) : 0ull;
@@ -159,39 +149,26 @@ __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) 
     T* dst = (T*)p.out;
     const bool aligned = ((uintptr_t)src & 15u) == 0;
     const int64_t padded = (p.n + 63) / 64 * 64;
-    for (int blk = 0; blk < kFillBlocks; ++blk) {
-        const int64_t first = tile * kFillTile + (int64_t)blk * kFillBlock;
+    for (int blk = 0; blk < kTileBlocks; ++blk) {
+        const int64_t first = tile * kTileRows + (int64_t)blk * kTileBlock;
         if (first >= p.n) break;
-        const int64_t base = first + (int64_t)t * kFillPer;
+        const int64_t base = first + (int64_t)t * kTilePer;
         if (base >= p.n) {  // the rest of the last validity word
             if (base < padded) p.out_valid[base >> 3] = 0;
             continue;
         }
-        const int wi = blk * (kFillBlock / 64) + (t >> 3);
-        const int b0 = (t & 7) * kFillPer;  // the thread's rows are bits b0 .. b0 + 7 of the word
+        const int wi = blk * (kTileBlock / 64) + (t >> 3);
+        const int b0 = (t & 7) * kTilePer;  // the thread's rows are bits b0 .. b0 + 7 of the word
         const uint64_t V = sV[wi], S = SEG ? sS[wi] : 0ull;
         const uint32_t vb = (uint32_t)(V >> b0) & 0xFFu, sb = (uint32_t)(S >> b0) & 0xFFu;
         (void)sb;
-        const bool full = base + kFillPer <= p.n;
-        T x[kFillPer];
+        const bool full = base + kTilePer <= p.n;
+        T x[kTilePer];
         if (full && aligned) {
-            if constexpr (BYTES == 8) {
-                const ulonglong2* s2 = (const ulonglong2*)(src + base);
-#pragma unroll
-                for (int k = 0; k < kFillPer / 2; ++k) {
-                    const ulonglong2 q = s2[k];
-                    x[2 * k] = q.x;
-                    x[2 * k + 1] = q.y;
-                }
-            } else {
-                const uint4* s4 = (const uint4*)(src + base);
-                const uint4 q0 = s4[0], q1 = s4[1];
-                x[0] = q0.x; x[1] = q0.y; x[2] = q0.z; x[3] = q0.w;
-                x[4] = q1.x; x[5] = q1.y; x[6] = q1.z; x[7] = q1.w;
-            }
+            load_vec8(src + base, x);
         } else {
 #pragma unroll
-            for (int k = 0; k < kFillPer; ++k) x[k] = base + k < p.n ? src[base + k] : (T)0;
+            for (int k = 0; k < kTilePer; ++k) x[k] = base + k < p.n ? src[base + k] : (T)0;
         }
         uint32_t ob = vb;
         if (vb != 0xFFu) {
@@ -199,7 +176,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) 
             // them in scan order, else the word's own entry codes
             uint64_t mj, ms;
             if constexpr (REV) {
-                const uint64_t after = b0 + kFillPer == 64 ? 0ull : ~0ull << (b0 + kFillPer);
+                const uint64_t after = b0 + kTilePer == 64 ? 0ull : ~0ull << (b0 + kTilePer);
                 mj = V & after;
                 ms = S & after;
             } else {
@@ -207,15 +184,15 @@ __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) 
                 mj = V & before;
                 ms = S & before;
             }
-            const int64_t r0 = (tile * kFillWords + wi) * 64;
+            const int64_t r0 = (tile * kTileWords + wi) * 64;
             uint64_t jc = mj ? fill_word_code<REV>(mj, r0) : sJ[wi];
             uint64_t sc = 0ull;
             if constexpr (SEG) sc = ms ? fill_word_code<REV>(ms, r0) : sT[wi];
             T val = (T)0;
             bool have = false;  // val holds x[j] of the row code jc
 #pragma unroll
-            for (int kk = 0; kk < kFillPer; ++kk) {
-                const int k = REV ? kFillPer - 1 - kk : kk;
+            for (int kk = 0; kk < kTilePer; ++kk) {
+                const int k = REV ? kTilePer - 1 - kk : kk;
                 const int64_t i = base + k;
                 const uint64_t ic = fill_row_code<REV>(i);
                 if constexpr (SEG) {
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) 
             if constexpr (BYTES == 8) {
                 ulonglong2* d2 = (ulonglong2*)(dst + base);
 #pragma unroll
-                for (int k = 0; k < kFillPer / 2; ++k) d2[k] = make_ulonglong2(x[2 * k], x[2 * k + 1]);
+                for (int k = 0; k < kTilePer / 2; ++k) d2[k] = make_ulonglong2(x[2 * k], x[2 * k + 1]);
             } else {
                 uint4* d4 = (uint4*)(dst + base);
                 d4[0] = make_uint4(x[0], x[1], x[2], x[3]);
@@ -248,7 +225,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(FillParams p) 
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < kFillPer; ++k)
+            for (int k = 0; k < kTilePer; ++k)
                 if (base + k < p.n) dst[base + k] = x[k];
         }
         p.out_valid[base >> 3] = (uint8_t)ob;  // rows past the column: zero bits
@@ -260,16 +237,16 @@ void fill_launch(const FillParams& p, hipStream_t s) {
     const unsigned g = (unsigned)p.tiles;
     {
         KtScope kt("fill_reduce_kernel", s);
-        fill_reduce_kernel<REV><<<g, kFillThreads, 0, s>>>(p);
+        fill_reduce_kernel<REV><<<g, kTileThreads, 0, s>>>(p);
     }
     {
         KtScope kt("fill_totals_kernel", s);
-        fill_totals_kernel<REV><<<1, kFillTotalsThreads, 0, s>>>(p);
+        fill_totals_kernel<REV><<<1, kTotalsThreads, 0, s>>>(p);
     }
     {
         KtScope kt("fill_apply_kernel", s);
-        if (p.seg) fill_apply_kernel<BYTES, REV, true><<<g, kFillThreads, 0, s>>>(p);
-        else fill_apply_kernel<BYTES, REV, false><<<g, kFillThreads, 0, s>>>(p);
+        if (p.seg) fill_apply_kernel<BYTES, REV, true><<<g, kTileThreads, 0, s>>>(p);
+        else fill_apply_kernel<BYTES, REV, false><<<g, kTileThreads, 0, s>>>(p);
     }
 }
 
@@ -285,10 +262,8 @@ PLGPU_API int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_sta
     std::memset(out, 0, sizeof *out);
     if (kind != PLGPU_FILL_FORWARD && kind != PLGPU_FILL_BACKWARD) return fail(PLGPU_ERR_INVALID, "unknown fill kind");
     if (seg_starts != nullptr) {
-        if (seg_starts->dtype != PLGPU_BOOL || seg_starts->validity != nullptr)
-            return fail(PLGPU_ERR_INVALID, "segment starts must be a null-free Boolean column");
-        if (seg_starts->length != values->length)
-            return fail(PLGPU_ERR_INVALID, "segment starts and values must have equal lengths");
+        const int rc = seg_check(values, seg_starts, PLGPU_ERR_INVALID, PLGPU_ERR_INVALID);
+        if (rc) return rc;
     }
     const int eb = dtype_bytes(values->dtype);
     if (eb != 4 && eb != 8)
@@ -325,7 +300,7 @@ PLGPU_API int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_sta
     p.limit = limit < 0 ? (uint64_t)INT64_MAX : (uint64_t)limit;
     p.out = (void*)out->values;
     p.out_valid = (uint8_t*)out->validity;
-    p.tiles = (n + kFillTile - 1) / kFillTile;
+    p.tiles = (n + kTileRows - 1) / kTileRows;
     DevBuf<uint64_t> carry;
     rc = carry.alloc((size_t)p.tiles * 8 * 2, s);
     if (!rc) {

@@ -263,6 +263,20 @@ inline DevCol dev_col(const plgpu_column& c) {
     return d;
 }
 
+// The checks of a segment-start column against its values.  The entry points
+// report them with different codes, which the tests pin: plgpu_cumulative,
+// plgpu_lag and plgpu_rolling_segmented pass (PLGPU_ERR_SCHEMA,
+// PLGPU_ERR_SHAPE), plgpu_fill and plgpu_ewm_mean PLGPU_ERR_INVALID for both.
+// One pair of codes for all five is a change of the ABI, left for its own.
+// (The bitmap as words for the kernels: seg_starts.hpp.)
+inline int seg_check(const plgpu_column* values, const plgpu_column* seg_starts, int type_code, int length_code) {
+    if (seg_starts->dtype != PLGPU_BOOL) return fail(type_code, "segment starts must be a Boolean column");
+    if (seg_starts->validity != nullptr) return fail(type_code, "segment starts must not be nullable");
+    if (seg_starts->length != values->length)
+        return fail(length_code, "segment starts and values must have equal lengths");
+    return PLGPU_OK;
+}
+
 // Owning PLGPU_STR column: n + 1 offsets, `bytes` of string data.
 int make_owned_string_column(plgpu_column* out, int64_t length, int64_t bytes, bool with_validity, hipStream_t s);
 // An owned I64 column of length + 1 offsets -> a PLGPU_STR column of

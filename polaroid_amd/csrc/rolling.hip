@@ -30,6 +30,7 @@
 
 #include "plgpu_internal.hpp"
 #include "scan.hpp"
+#include "seg_starts.hpp"
 
 namespace plgpu {
 
@@ -73,14 +74,6 @@ struct RlSegParams : RlParams {
 };
 template <bool SEG>
 using RlP = typename std::conditional<SEG, RlSegParams, RlParams>::type;
-
-__device__ __forceinline__ uint64_t seg_word(const uint64_t* seg, int64_t nbytes, int64_t wi) {
-    if ((wi + 1) * 8 <= nbytes) return seg[wi];
-    uint64_t v = 0;  // the last, partial word byte by byte (a caller's bitmap need not be padded)
-    const uint8_t* b = (const uint8_t*)seg;
-    for (int64_t j = wi * 8; j < nbytes; ++j) v |= (uint64_t)b[j] << (8 * (j - wi * 8));
-    return v;
-}
 
 // The last segment start at or before row i, looking no further back than
 // row lo (<= i): lo when there is none after it.
@@ -1814,17 +1807,6 @@ static void rl_launch_seg(const RlSegParams& p, bool var, bool nl, bool hot, boo
     }
 }
 
-// Bits [off, off + n) of a bitmap as words from bit 0 (a segment-start
-// column with an offset or a values pointer that is not 8-byte aligned).
-__global__ __launch_bounds__(256) void seg_repack_kernel(DevCol c, int64_t n, uint64_t* __restrict__ out) {
-    const int64_t words = (n + 63) / 64;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < words * 64;
-         r += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t m = __ballot(r < n && dev_load(c, r) != 0);
-        if ((threadIdx.x & 63) == 0) out[r >> 6] = m;
-    }
-}
-
 static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_starts, int32_t kind,
                         int64_t window_size, int64_t min_periods, int32_t center, plgpu_column* out, void* stream) {
     hipStream_t s = as_stream(stream);
@@ -1832,10 +1814,8 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
     std::memset(out, 0, sizeof *out);
     const bool segd = seg_starts != nullptr;
     if (segd) {
-        if (seg_starts->dtype != PLGPU_BOOL) return fail(PLGPU_ERR_SCHEMA, "segment starts must be a Boolean column");
-        if (seg_starts->validity != nullptr) return fail(PLGPU_ERR_SCHEMA, "segment starts must not be nullable");
-        if (seg_starts->length != values->length)
-            return fail(PLGPU_ERR_SHAPE, "segment starts and values must have equal lengths");
+        const int rc = seg_check(values, seg_starts, PLGPU_ERR_SCHEMA, PLGPU_ERR_SHAPE);
+        if (rc) return rc;
     }
     // bits 8..15: ddof; bit 16 (std of a Float32 column): the variance is
     // rounded to Float32 before the square root, as the reference's f32 sqrt
@@ -1850,24 +1830,11 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
     if (min_periods < 0) return fail(PLGPU_ERR_INVALID, "min_periods must be >= 0");
     if (min_periods > window_size)
         return fail(PLGPU_ERR_INVALID, "`min_periods` should be <= `window_size`");
-    // the bitmap as 8-byte words from bit 0: the column's own buffer where
-    // it is laid out so (as plgpu_segment_starts writes it), else a copy
     const uint64_t* seg = nullptr;
     DevBuf<uint64_t> seg_own;
     if (segd && values->length > 0) {
-        const uintptr_t at = (uintptr_t)seg_starts->values + (uintptr_t)(seg_starts->offset / 8);
-        if (seg_starts->offset % 8 == 0 && at % 8 == 0) {
-            seg = (const uint64_t*)at;
-        } else {
-            const int64_t words = (values->length + 63) / 64;
-            int rc = seg_own.alloc((size_t)words * 8, s);
-            if (rc) return rc;
-            seg_repack_kernel<<<(unsigned)std::min<int64_t>((words * 64 + 255) / 256, 256 * 64), 256, 0, s>>>(
-                dev_col(*seg_starts), values->length, seg_own);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "segment starts");
-            seg = seg_own;
-        }
+        const int rc = seg_words(seg_starts, values->length, seg_own, &seg, s);
+        if (rc) return rc;
     }
     if (kind == PLGPU_ROLLING_MIN || kind == PLGPU_ROLLING_MAX)
         return rolling_minmax(values, seg, kind == PLGPU_ROLLING_MAX, window_size, min_periods, center != 0, out, s);

@@ -229,7 +229,7 @@ class Expr:
             raise N.InvalidOperationError(
                 f"{self!r}.{op}(): a window expression (over) inside an aggregation's input is not supported "
                 "on the GPU executor")
-        if _has_cum_lag(self):
+        if _has_scan(self):
             raise N.InvalidOperationError(
                 f"{self!r}.{op}(): a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / "
                 "backward_fill / fill_null(strategy=...) / ewm_mean) inside an aggregation's input is not supported "
@@ -381,7 +381,7 @@ class Expr:
         f = self
         while f.kind == "alias":
             f = f.args[0]
-        if f.kind in ("rolling", "cum", "lag", "fill", "ewm"):
+        if f.kind == "rolling" or f.kind in _SCAN_KINDS:
             ok = _is_elementwise(f.args[0])
         elif f.kind == "agg":
             ok = f.op in _OVER_AGGS and _is_elementwise(f.args[0])
@@ -420,7 +420,7 @@ def _is_rowwise(e: Expr) -> bool:
     them: one value per row, in row order."""
     if e.kind == "over":
         return True
-    return e.kind in _ELEMENTWISE + ("rolling", "cum", "lag", "fill", "ewm") and builtins.all(_is_rowwise(a) for a in e.args)
+    return e.kind in _ELEMENTWISE + ("rolling",) + _SCAN_KINDS and builtins.all(_is_rowwise(a) for a in e.args)
 
 
 def _lag_input(e: Expr, what: str) -> None:
@@ -510,8 +510,8 @@ def _fill(e: Expr, strategy: str, limit: Any) -> Expr:
     return Expr("fill", (e,), op=strategy, value=(_fill_limit(limit),))
 
 
-def _has_cum_lag(e: Expr) -> bool:
-    return e.kind in ("cum", "lag", "fill", "ewm") or builtins.any(_has_cum_lag(a) for a in e.args)
+def _has_scan(e: Expr) -> bool:
+    return e.kind in _SCAN_KINDS or builtins.any(_has_scan(a) for a in e.args)
 
 
 def _prepare_alpha(com: Any = None, span: Any = None, half_life: Any = None, alpha: Any = None) -> float:
@@ -556,6 +556,7 @@ def _ewm_min_samples(v: Any) -> int:
 
 
 _OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")
+_SCAN_KINDS = ("cum", "lag", "fill", "ewm")  # the segmented scans (frame._window_fn; csrc/seg_scan.hpp)
 _ELEMENTWISE = ("col", "lit", "bin", "un", "alias", "ternary", "cast", "fill_null", "strfn", "over")
 
 

@@ -16,8 +16,8 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _native as N
-from .expr import (Expr, _ewm_min_samples, _fill_args, _fill_limit, _has_cum_lag, _has_over, _lag_n, _prepare_alpha,
-                   col, lit, lower, to_instr_array)
+from .expr import (_SCAN_KINDS, Expr, _ewm_min_samples, _fill_args, _fill_limit, _has_over, _has_scan, _lag_n,
+                   _prepare_alpha, col, lit, lower, to_instr_array)
 
 
 # ------------------------------------------------------------------ dtypes
@@ -1218,7 +1218,7 @@ class LazyFrame:
             raise N.InvalidOperationError(
                 "a window expression (over) in a filter predicate is not supported on the GPU executor: "
                 "compute it with with_columns first and filter on that column")
-        if _has_cum_lag(pred):
+        if _has_scan(pred):
             raise N.InvalidOperationError(
                 "a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / backward_fill / "
                 "fill_null(strategy=...) / ewm_mean) in a filter predicate is not supported on the GPU executor: compute it "
@@ -1687,25 +1687,11 @@ def _over_segments(keys: Sequence[str], df: DataFrame, cache: dict | None) -> tu
     return seg
 
 
-def _over_rolling(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
-    """<elementwise>.rolling_*(...).over(keys): keys that arrive sorted need
-    one pass for the segment starts and the segmented kernel; otherwise a
-    stable sort by the keys, the same two steps on the gathered rows, and a
-    gather back through the inverse permutation (window.rs:524
-    MapStrategy::Map)."""
-    vals = _eval(f.args[0], df, cache)
-    w, ms, center, ddof = f.value
-    kind = N.ROLLING[f.op]
-    starts, idx_s, inv = _over_segments(keys, df, cache)
-    if starts.len() != vals.len():
-        raise N.ShapeError("over(): the partition keys and the values differ in length")
-    if idx_s is None:
-        return vals._rolling(kind, w, ms, center, ddof, seg=starts)
-    return vals.gather(idx_s)._rolling(kind, w, ms, center, ddof, seg=starts).gather(inv)
-
-
-def _cum_lag(f: Expr, vals: Series, seg: Series | None = None) -> Series:
-    """A "cum" / "lag" / "fill" / "ewm" node on its evaluated input."""
+def _window_fn(f: Expr, vals: Series, seg: Series | None = None) -> Series:
+    """A "rolling" or scan ("cum" / "lag" / "fill" / "ewm") node on its
+    evaluated input, per segment when `seg` holds the segment starts."""
+    if f.kind == "rolling":
+        return vals._rolling(N.ROLLING[f.op], *f.value, seg=seg)
     if f.kind == "cum":
         return vals._cum(f.op, f.value[0], seg=seg)
     if f.kind == "ewm":
@@ -1717,13 +1703,15 @@ def _cum_lag(f: Expr, vals: Series, seg: Series | None = None) -> Series:
     return vals._lag(f.op, f.value[0], f.value[1] if f.op == "shift" else None, seg=seg)
 
 
-def _over_cum_lag(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
-    """<elementwise>.cum_*() / .shift(...) / .diff(...) / .forward_fill(...) /
-    .backward_fill(...).over(keys), routed as _over_rolling: presorted keys
-    cost the segment starts and the function's kernels, otherwise sort,
-    gather, kernels and the gather back.  fill_null(strategy = zero / one) is
-    the plain fill; min / max / mean fill with the group's aggregate
-    (_over_agg) through the elementwise fill_null."""
+def _over_window(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None = None) -> Series:
+    """<elementwise>.rolling_*(...) / .cum_*() / .shift(...) / .diff(...) /
+    .forward_fill(...) / .backward_fill(...) / .ewm_mean(...).over(keys): keys
+    that arrive sorted need one pass for the segment starts and the function's
+    segmented kernels; otherwise a stable sort by the keys, the same two steps
+    on the gathered rows, and a gather back through the inverse permutation
+    (window.rs:524 MapStrategy::Map).  fill_null(strategy = zero / one) is the
+    plain fill; min / max / mean fill with the group's aggregate (_over_agg)
+    through the elementwise fill_null."""
     vals = _eval(f.args[0], df, cache)
     if f.kind == "fill" and f.op not in ("forward", "backward"):
         if f.op in ("zero", "one") or vals.dtype is String or vals._col.dtype == N.BOOL \
@@ -1740,9 +1728,9 @@ def _over_cum_lag(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | Non
     if starts.len() != vals.len():
         raise N.ShapeError("over(): the partition keys and the values differ in length")
     if idx_s is None:
-        res = _cum_lag(f, vals, starts)
+        res = _window_fn(f, vals, starts)
     else:
-        res = _cum_lag(f, vals.gather(idx_s), starts).gather(inv)
+        res = _window_fn(f, vals.gather(idx_s), starts).gather(inv)
     return Series._categorical(res.name, cc[0], res) if cc is not None else res
 
 
@@ -1763,13 +1751,13 @@ def _over_agg(f: Expr, keys: Sequence[str], df: DataFrame) -> Series:
     return out["__over_agg"]
 
 
-def _cum_lag_below(e: Expr, top: bool = True) -> bool:
-    """Is a cum / lag node anywhere but at the top (under its alias) of e?"""
+def _scan_below(e: Expr, top: bool = True) -> bool:
+    """Is a scan node (_SCAN_KINDS) anywhere but at the top (under its alias) of e?"""
     if e.kind == "alias":
-        return _cum_lag_below(e.args[0], top)
-    if e.kind in ("cum", "lag", "fill", "ewm") and not top:
+        return _scan_below(e.args[0], top)
+    if e.kind in _SCAN_KINDS and not top:
         return True
-    return builtins.any(_cum_lag_below(a, False) for a in e.args)
+    return builtins.any(_scan_below(a, False) for a in e.args)
 
 
 def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list, top: bool = True) -> Expr:
@@ -1780,18 +1768,16 @@ def _over_walk(e: Expr, df: DataFrame, cache: dict | None, extra: list, top: boo
         f = e.args[0]
         while f.kind == "alias":
             f = f.args[0]
-        if f.kind == "rolling":
-            res = _over_rolling(f, e.value, df, cache)
-        elif f.kind in ("cum", "lag", "fill", "ewm"):
-            res = _over_cum_lag(f, e.value, df, cache)
+        if f.kind == "rolling" or f.kind in _SCAN_KINDS:
+            res = _over_window(f, e.value, df, cache)
         else:
             res = _over_agg(f, e.value, df)
         name = f"__over{builtins.len(extra)}"
         extra.append(res.alias(name))
         return col(name)
-    if e.kind in ("cum", "lag", "fill", "ewm") and not top:
+    if e.kind in _SCAN_KINDS and not top:
         # inside a larger expression (x / x.shift(1) - 1): a temporary column too
-        res = _cum_lag(e, _eval(e.args[0], df, cache))
+        res = _window_fn(e, _eval(e.args[0], df, cache))
         name = f"__over{builtins.len(extra)}"
         extra.append(res.alias(name))
         return col(name)
@@ -1816,7 +1802,7 @@ def _lower_overs(expr: Expr, df: DataFrame, cache: dict | None = None) -> tuple[
 def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
     """`overs`: what the over() nodes of one select / with_columns share
     (_over_segments), valid for this `df` alone."""
-    if _has_over(expr) or _cum_lag_below(expr):
+    if _has_over(expr) or _scan_below(expr):
         name = expr.output_name()
         expr, df = _lower_overs(expr, df, overs)
         return _eval(expr, df).alias(name)
@@ -1826,15 +1812,14 @@ def _eval(expr: Expr, df: DataFrame, overs: dict | None = None) -> Series:
     if base.kind in ("rolling", "sort"):
         inner = _eval(base.args[0], df)
         if base.kind == "rolling":
-            w, ms, center, ddof = base.value
-            res = inner._rolling(N.ROLLING[base.op], w, ms, center, ddof)
+            res = _window_fn(base, inner)
         elif base.op == "arg_sort":
             res = inner.arg_sort(descending=base.value[0], nulls_last=base.value[1])
         else:
             res = inner.sort(descending=base.value[0], nulls_last=base.value[1])
         return res.alias(expr.output_name())
-    if base.kind in ("cum", "lag", "fill", "ewm"):
-        return _cum_lag(base, _eval(base.args[0], df)).alias(expr.output_name())
+    if base.kind in _SCAN_KINDS:
+        return _window_fn(base, _eval(base.args[0], df)).alias(expr.output_name())
     expr, df = _lower_strings(expr, df)
     name = expr.output_name()
     expr, logical, strict = _prepare(expr, df)
@@ -1982,7 +1967,7 @@ def _gb_lower(df: DataFrame, key: str | tuple | None, aggs: list[Expr], pred: Ex
             exprs.append(x)
             specs.append((base.op, ("input", builtins.len(exprs) - 1)))
             out_logical.append(lg if base.op in ("min", "max", "first", "last", "sum") else None)
-        elif base.kind in ("cum", "lag", "fill", "ewm"):
+        elif base.kind in _SCAN_KINDS:
             raise N.InvalidOperationError(
                 f"{e!r} is not an aggregation: cum_* / shift / diff / forward_fill / backward_fill / "
                 "fill_null(strategy=...) / ewm_mean give one value per row and are not supported inside group_by().agg() on "

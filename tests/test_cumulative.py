@@ -345,17 +345,19 @@ def test_native_tables(N):
     assert N.CUM == {"sum": 1, "min": 2, "max": 3, "count": 4}
     assert N.LAG == {"shift": 1, "diff": 2}
     assert N.CUM_TILE >= 64 and N.CUM_TILE % 64 == 0
-    # CUM_TILE mirrors kCumTile = kCumThreads * kCumPer * kCumBlocks
+    # CUM_TILE mirrors kTileRows = kTileThreads * kTilePer * kTileBlocks of the shared scan header
     import os
     import re
 
     from conftest import ROOT
 
-    src = open(os.path.join(ROOT, "polaroid_amd", "csrc", "cumulative.hip")).read()
-    th = int(re.search(r"kCumThreads = (\d+);", src).group(1))
-    per = int(re.search(r"kCumPer = (\d+);", src).group(1))
-    blocks = int(re.search(r"kCumBlocks = (\d+);", src).group(1))
-    assert th * per == N.CUM_BLOCK and th * per * blocks == N.CUM_TILE
+    src = open(os.path.join(ROOT, "polaroid_amd", "csrc", "seg_scan.hpp")).read()
+    th = int(re.search(r"kTileThreads = (\d+);", src).group(1))
+    per = int(re.search(r"kTilePer = (\d+);", src).group(1))
+    blocks = int(re.search(r"kTileBlocks = (\d+);", src).group(1))
+    totals = int(re.search(r"kTotalsThreads = (\d+);", src).group(1))
+    assert th * per == N.CUM_BLOCK and th * per * blocks == N.CUM_TILE == 16384
+    assert N.CUM_THREADS == th and N.CUM_TOTALS_THREADS == totals
 
 
 def test_cumulative_argument_checks(N):

@@ -321,17 +321,22 @@ def _host_col(N, dtype, n, nullable=False):
 def test_native_tables(N):
     assert N.FILL == {"forward": 1, "backward": 2}
     assert "plgpu_fill" in N.SIGNATURES and len(N.SIGNATURES["plgpu_fill"][1]) == 6
-    # the fill kernels' tile is the scans' (kFillTile = kCumTile)
+    # the fill kernels' tile is the scans': one geometry in the shared header, none of its own
     import os
     import re
 
     from conftest import ROOT
 
-    src = open(os.path.join(ROOT, "polaroid_amd", "csrc", "fill.hip")).read()
-    th = int(re.search(r"kFillThreads = (\d+);", src).group(1))
-    per = int(re.search(r"kFillPer = (\d+);", src).group(1))
-    blocks = int(re.search(r"kFillBlocks = (\d+);", src).group(1))
+    csrc = os.path.join(ROOT, "polaroid_amd", "csrc")
+    src = open(os.path.join(csrc, "seg_scan.hpp")).read()
+    th = int(re.search(r"kTileThreads = (\d+);", src).group(1))
+    per = int(re.search(r"kTilePer = (\d+);", src).group(1))
+    blocks = int(re.search(r"kTileBlocks = (\d+);", src).group(1))
+    totals = int(re.search(r"kTotalsThreads = (\d+);", src).group(1))
     assert th * per == N.CUM_BLOCK and th * per * blocks == N.CUM_TILE == 16384
+    assert N.CUM_THREADS == th and N.CUM_TOTALS_THREADS == totals
+    for f in ("cumulative.hip", "fill.hip", "ewm.hip"):
+        assert not re.search(r"k(Cum|Fill|Ewm)(Threads|Per|Blocks?|Tile|Words|TotalsThreads)\b", open(os.path.join(csrc, f)).read())
 
 
 def test_fill_argument_checks(N):

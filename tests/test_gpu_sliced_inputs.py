@@ -54,9 +54,11 @@ The alignment gates, and the layouts that drive each to either side
       var rows on the generic and partitioned paths at off2 / off1
       (test_var_split_at_an_offset).
   Series.slice's null_count == -1: test_null_count_unknown.
-  join.hip / sort.hip / rolling.hip (:1858 rolling_segmented's start bitmap
-      in place where the slice begins on an aligned 8-byte word, its repack
-      otherwise: test_rolling_segmented_start_column) / strings.hip /
+  join.hip / sort.hip / rolling.hip (seg_starts.hpp seg_words: the start
+      bitmap in place where the slice begins on an aligned 8-byte word, its
+      repack otherwise: test_rolling_segmented_start_column; the same column
+      into cumulative / lag, and at its own bit offset into fill / ewm:
+      test_scans_segmented_start_column) / strings.hip /
       shuffle.hip / the interpreter's dev_load / dev_valid: section B below,
       on fresh / off1 / off2 / off63 / off64 / off65 / mixed.
 """
@@ -68,6 +70,9 @@ import numpy as np
 import pytest
 
 import polaroid_amd as pl
+import test_gpu_cumulative as TC
+import test_gpu_ewm as TE
+import test_gpu_fill as TF
 from oracle import oracle as O
 from polaroid_amd import _native as N
 from polaroid_amd._native import fused_variant
@@ -780,6 +785,65 @@ def test_rolling_segmented_start_column(gpu, soff):
                 ev[rows], eok[rows] = e, ok
             assert np.array_equal(gok, eok), (soff, kind, w)
             assert np.array_equal(_bits(gv[gok]), _bits(ev[eok])), (soff, kind, w)
+
+
+SCAN_N = N.CUM_TILE + N.CUM_BLOCK + 5  # one tile, one block and a ragged tail: a carry, a block hand-over, a partial word
+
+
+@functools.lru_cache(maxsize=None)
+def _scan_host():
+    """The columns of test_scans_segmented_start_column and what every scan
+    must give, by the per-segment numpy folds of the operators' own modules."""
+    rng = np.random.default_rng(45)
+    n = SCAN_N
+    valid = rng.random(n) > 0.1
+    starts = np.append(True, rng.random(n - 1) < 0.01)
+    starts[-1] = False  # the junk after the slice is its inverse: set bits
+    i64 = rng.integers(-10**12, 10**12, n).astype(np.int64)
+    f64 = rng.uniform(-50, 50, n)
+    first = TC._seg_info(starts)
+    exp = {("cum", "sum"): TC._ref(i64, valid, first, "sum"), ("cum", "max"): TC._ref(f64, valid, first, "max"),
+           ("lag", "shift", 1): TC._lag_ref(f64, valid, first, "shift", 1),
+           ("lag", "diff", 2): TC._lag_ref(f64, valid, first, "diff", 2)}
+    for op in ("forward", "backward"):
+        exp["fill", op] = TF._ref(f64, valid, op, 3, starts)
+    return valid, starts, i64, f64, exp
+
+
+def _start_column(starts, soff):
+    """The Boolean start column sliced at bit `soff`, or ("borrowed") at bit 2
+    of a bitmap that begins 3 bytes into its allocation."""
+    if soff != "borrowed":
+        seg = _place("seg", starts, None, "slice", soff)
+        assert seg._keep[0].to_numpy()[soff + starts.size:].all()
+        return seg
+    pv, _ = _parent(starts, None, 2)
+    assert pv[2 + starts.size:].all()
+    buf = _upload_bytes(np.packbits(pv, bitorder="little"), 3)
+    return pl.Series.from_device("seg", pl.Boolean, buf.ptr + 3, starts.size, offset=2, keepalive=[buf])
+
+
+@pytest.mark.parametrize("soff", [64, 8, 3, "borrowed"])
+def test_scans_segmented_start_column(gpu, soff):
+    """plgpu_cumulative, plgpu_lag, plgpu_fill and plgpu_ewm_mean with the
+    Boolean start column of test_rolling_segmented_start_column: offset 64
+    (used in place by the two that read whole words), 8 (a whole byte but no
+    aligned word), 3, and a borrowed bitmap at an odd byte address; the
+    parent's bits are set in the junk after the slice."""
+    valid, starts, i64, f64, exp = _scan_host()
+    seg = _start_column(starts, soff)
+    xi, xf = _place("x", i64, valid, "slice", 66), _place("x", f64, valid, "slice", 66)
+    TC._assert_same(*TC._cum(xi, "sum", seg), *exp["cum", "sum"], (soff, "cum_sum"))
+    TC._assert_same(*TC._cum(xf, "max", seg), *exp["cum", "max"], (soff, "cum_max"), bits=True)
+    for op, k in (("shift", 1), ("diff", 2)):
+        (gv, gok), (ev, eok) = TC._lag(xf, op, k, seg), exp["lag", op, k]
+        assert np.array_equal(gok, eok), (soff, op, "validity")
+        assert gv[eok].tobytes() == ev[eok].tobytes(), (soff, op)
+    for op in ("forward", "backward"):
+        TF._same(TF._fill(xf, op, 3, seg), exp["fill", op], (soff, op))
+    for adjust in (True, False):
+        TE._check(TE._ewm(xf, 0.3, adjust, False, seg=seg), f64, valid, 0.3, adjust, False, (soff, "ewm", adjust),
+                  starts=starts)
 
 
 # --------------------------------------------------- B. eval and filter
