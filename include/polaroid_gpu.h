@@ -310,6 +310,11 @@ int plgpu_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
  *                  no sort and no gather; 0: it sorts all the same (same
  *                  results).  Read by the caller choosing the path (the host
  *                  mirror's over()); the entry points do not depend on it
+ *   "asof_path"    plgpu_join_asof without ranges: 0 the library decides
+ *                  (today: as 1), 1 every tile of left rows searches the
+ *                  window of the right column its keys can touch, staged in
+ *                  LDS where it fits, 2 every row searches the whole right
+ *                  column (tests / A-B; results never depend on it)
  * An unknown name is PLGPU_ERR_INVALID. */
 int plgpu_set_option(const char* name, int64_t value);
 int plgpu_get_option(const char* name, int64_t* out);
@@ -948,6 +953,66 @@ int plgpu_fill(const plgpu_column* values, const plgpu_column* seg_starts /* NUL
 int plgpu_ewm_mean(const plgpu_column* values, const plgpu_column* seg_starts /* NULL: one segment */,
                    double alpha, int32_t adjust, int32_t ignore_nulls, int64_t min_samples,
                    plgpu_column* out, void* stream);
+
+/* ---- as-of join -----------------------------------------------------------------
+ * plgpu_join_asof: for every left row the row of the right side whose `on` key
+ * is the closest at or before (BACKWARD), at or after (FORWARD) or on either
+ * side (NEAREST) of the left key: a left join in left-row order, as one UInt32
+ * index column with validity, the form plgpu_join writes for a left join and
+ * plgpu_gather takes.  Replaces polars-ops/src/frame/join/asof/mod.rs:46-199
+ * (AsofJoinForwardState / BackwardState / NearestState::next), default.rs:11
+ * join_asof_impl and :112 join_asof_numeric, and with ranges groups.rs:38
+ * asof_in_group.  The reference walks both sides with one running state; for
+ * ascending right keys its answer is a function of each left key alone, which
+ * is what is computed here.  With lb(x) the first position of the non-null
+ * right keys whose value is >= x and ub(x) the first whose value is > x:
+ *   BACKWARD  ub(l) - 1 (allow_eq: the last of a run of equal values), else
+ *             lb(l) - 1; nothing before the first value.
+ *   FORWARD   lb(l) (allow_eq: the first of a run), else ub(l); nothing past
+ *             the end.
+ *   NEAREST   with allow_eq and a value equal to l, ub(l) - 1.  Otherwise
+ *             lower = lb(l) - 1 and upper = the last of the run of equal
+ *             values that begins at ub(l); one side missing takes the other;
+ *             upper when abs_diff(l, upper) <= abs_diff(l, lower), else lower.
+ *   tolerance (has_tolerance != 0): the one match chosen above is kept only if
+ *             abs_diff(l, r) <= |tolerance|; no other candidate is looked for.
+ *             Integer keys take tolerance_bits (an Int64; the bits of a UInt64
+ *             for UInt64 keys), float keys tolerance_f64 (rounded to the key's
+ *             type).
+ *   abs_diff  integers: the exact unsigned difference; floats: |l - r| in the
+ *             key's own type (a NaN difference passes no tolerance).
+ * Floats compare by TotalOrd (-0.0 == 0.0, NaN greatest and equal to itself);
+ * the reference's partial_cmp stalls its scan at a NaN.  A null left key, and
+ * every row when all right keys are null, gets no match.  The right keys are
+ * taken to be ascending with their nulls first; on other input the result is
+ * unspecified, and every index is still null or a row of the right side.
+ * lo / hi (both or neither; null-free UInt32 columns of the left length): left
+ * row i searches positions [lo[i], hi[i]) of the right column only, clamped
+ * into [0, length] (a reversed range is empty); the right column then has no
+ * validity buffer.  right_rows (a null-free UInt32 column of the right length,
+ * or NULL): the index written is right_rows[position].  *out_path (optional):
+ * 1 the window search (option "asof_path"), 2 the whole-column search, 3 ranges.
+ * Keys: Int32 / Int64 / UInt32 / UInt64 / Float32 / Float64, both sides alike.
+ * PLGPU_ERR_INVALID: a NULL left_on / right_on / out_idx, an unknown strategy,
+ * lo without hi, lo / hi / right_rows of another dtype or length or with a
+ * validity buffer, ranges with a nullable right column, a right side of
+ * 2^32 - 1 rows or more; PLGPU_ERR_SCHEMA: unequal or other key dtypes; all
+ * before any device work.  Empty sides are legal.
+ * One launch (two when the right column has a validity buffer: its first
+ * non-null row is found first); no workgroup waits on another.
+ *
+ * plgpu_is_sorted_asc: one pass over a column of those dtypes.
+ * *out_nulls_first = 1 when no null follows a non-null row; *out_ascending = 1
+ * when no non-null value is smaller (TotalOrd) than a non-null value right
+ * before it.  Both together are the reference's ensure_sorted_arg with the
+ * default SortOptions (polars-ops/src/series/ops/various.rs:69). */
+enum plgpu_asof_strategy { PLGPU_ASOF_BACKWARD = 0, PLGPU_ASOF_FORWARD = 1, PLGPU_ASOF_NEAREST = 2 };
+int plgpu_join_asof(const plgpu_column* left_on, const plgpu_column* right_on,
+                    const plgpu_column* lo /* NULL: the whole right column */, const plgpu_column* hi,
+                    const plgpu_column* right_rows /* NULL: positions are rows */, int32_t strategy,
+                    int32_t allow_eq, int32_t has_tolerance, int64_t tolerance_bits, double tolerance_f64,
+                    plgpu_column* out_idx, int32_t* out_path, void* stream);
+int plgpu_is_sorted_asc(const plgpu_column* col, int32_t* out_ascending, int32_t* out_nulls_first, void* stream);
 
 #ifdef __cplusplus
 }

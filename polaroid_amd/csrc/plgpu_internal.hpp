@@ -85,6 +85,9 @@ struct Options {
     // window expressions over groups: 1 plgpu_segment_starts reports keys it finds sorted (no sort, no
     // gather in Expr.over), 0 it never does, so every over() takes the sort path (tests / A-B)
     int over_presorted = 1;
+    // as-of join without ranges (asof.hip): 0 / 1 every tile of left rows searches the window of the right
+    // column its keys can touch (staged in LDS where it fits), 2 every row searches the whole column (tests / A-B)
+    int asof_path = 0;
 };
 Options& options();
 

@@ -88,6 +88,7 @@ const OptField kOptFields[] = {
     {"join_radix_keys", "PLGPU_JOIN_RADIX_KEYS", &Options::join_radix_keys},
     {"join_radix_load", "PLGPU_JOIN_RADIX_LOAD", &Options::join_radix_load},
     {"join_radix_batch", "PLGPU_JOIN_RADIX_BATCH", &Options::join_radix_batch},
+    {"asof_path", "PLGPU_ASOF_PATH", &Options::asof_path},
 };
 const OptField* opt_field(const char* name) {
     for (const OptField& f : kOptFields)

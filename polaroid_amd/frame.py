@@ -1167,6 +1167,21 @@ class DataFrame:
                                 validate=validate, nulls_equal=nulls_equal, coalesce=coalesce,
                                 maintain_order=maintain_order).collect()
 
+    def join_asof(self, other: "DataFrame", *, left_on: Any = None, right_on: Any = None, on: Any = None,
+                  by_left: Any = None, by_right: Any = None, by: Any = None, strategy: str = "backward",
+                  suffix: str = "_right", tolerance: Any = None, allow_parallel: bool = True,
+                  force_parallel: bool = False, coalesce: bool = True, allow_exact_matches: bool = True,
+                  check_sortedness: bool = True) -> "DataFrame":
+        """Eager as-of join (py-polars DataFrame.join_asof): runs the lazy plan."""
+        for what, v in ((("on", on),) if on is not None else (("left_on", left_on), ("right_on", right_on))):
+            if not isinstance(v, (str, Expr)):
+                raise TypeError(f"expected `{what}` to be str or Expr, got {type(v).__name__!r}")
+        return self.lazy().join_asof(other.lazy(), left_on=left_on, right_on=right_on, on=on, by_left=by_left,
+                                     by_right=by_right, by=by, strategy=strategy, suffix=suffix, tolerance=tolerance,
+                                     allow_parallel=allow_parallel, force_parallel=force_parallel, coalesce=coalesce,
+                                     allow_exact_matches=allow_exact_matches,
+                                     check_sortedness=check_sortedness).collect()
+
     def group_by(self, *by: Any, maintain_order: bool = False) -> "GroupBy":
         return GroupBy(self.lazy(), by, maintain_order)
 
@@ -1207,7 +1222,8 @@ def _combine_predicates(preds: Sequence[Expr], constraints: dict) -> Expr:
 
 class LazyFrame:
     """A logical plan: ('scan', df) | ('filter', input, pred) | ('group_by', input,
-    keys, aggs, maintain_order) | ('select' / 'with_columns', input, exprs)."""
+    keys, aggs, maintain_order) | ('select' / 'with_columns', input, exprs) |
+    ('join' / 'join_asof', left, right, ...) | ('sort', input, ...)."""
 
     def __init__(self, node: tuple):
         self._node = node
@@ -1279,6 +1295,52 @@ class LazyFrame:
             raise ValueError(f"invalid `maintain_order` argument {maintain_order!r}")
         return LazyFrame(("join", self._node, other._node, left_on, right_on, suffix, validate, bool(nulls_equal),
                           maintain_order, how, coalesce))
+
+    def join_asof(self, other: "LazyFrame", *, left_on: Any = None, right_on: Any = None, on: Any = None,
+                  by_left: Any = None, by_right: Any = None, by: Any = None, strategy: str = "backward",
+                  suffix: str = "_right", tolerance: Any = None, allow_parallel: bool = True,
+                  force_parallel: bool = False, coalesce: bool = True, allow_exact_matches: bool = True,
+                  check_sortedness: bool = True) -> "LazyFrame":
+        """As-of join (py-polars LazyFrame.join_asof, lazyframe/frame.py:5263;
+        polars-ops/src/frame/join/asof): a left join on the nearest `on` key
+        (strategy backward / forward / nearest), inside equal `by` tuples when
+        given, within `tolerance` (a number in the key's unit, or for temporal
+        keys a timedelta or a duration string of ns us ms s m h d w).
+        `allow_parallel` / `force_parallel` are accepted and ignored."""
+        if isinstance(on, (str, Expr)):
+            left_on = right_on = on
+        if left_on is None or right_on is None:
+            raise ValueError("you should pass the column to join on as an argument")
+        names = []
+        for what, v in (("left_on", left_on), ("right_on", right_on)):
+            if isinstance(v, Expr):
+                if v.kind != "col":
+                    raise N.InvalidOperationError(
+                        f"join_asof: `{what}` as a computed expression is not supported on the GPU executor: "
+                        "compute it with with_columns first and join on that column")
+                v = v.value
+            if not isinstance(v, str):
+                raise TypeError(f"expected `{what}` to be str or Expr, got {type(v).__name__!r}")
+            names.append(v)
+        if by is not None:
+            by_left = by_right = by
+        if (by_left is None) != (by_right is None):
+            raise N.InvalidOperationError("expected both 'by_left' and 'by_right' to be set in 'asof_join'")
+        if by_left is not None:
+            by_left = (by_left,) if isinstance(by_left, str) else tuple(by_left)
+            by_right = (by_right,) if isinstance(by_right, str) else tuple(by_right)
+            if builtins.len(by_left) != builtins.len(by_right):
+                raise N.InvalidOperationError(
+                    "expected equal number of columns in 'by_left' and 'by_right' in 'asof_join'")
+            if not 1 <= builtins.len(by_left) <= N.MAX_KEYS or not builtins.all(
+                    isinstance(b, str) for b in by_left + by_right):
+                raise N.InvalidOperationError("the GPU executor takes 1..8 plain column names as join_asof `by` keys")
+        if strategy not in N.ASOF:
+            raise ValueError(f"invalid `strategy` argument {strategy!r}: expected backward, forward or nearest")
+        if isinstance(tolerance, str):
+            _duration_ns(tolerance)  # a malformed string is refused where the plan is built
+        return LazyFrame(("join_asof", self._node, other._node, names[0], names[1], by_left, by_right, strategy,
+                          suffix, tolerance, bool(coalesce), bool(allow_exact_matches), bool(check_sortedness)))
 
     def select(self, *exprs: Any) -> "LazyFrame":
         return LazyFrame(("select", self._node, _parse_exprs(exprs)))
@@ -1353,6 +1415,11 @@ def _explain(node: tuple, depth: int = 0) -> str:
     if kind == "join":
         return (f"{pad}INNER JOIN ON {node[3]} = {node[4]}\n" + _explain(node[1], depth + 1) + "\n"
                 + _explain(node[2], depth + 1))
+    if kind == "join_asof":
+        by = f" BY {builtins.list(node[5])} = {builtins.list(node[6])}" if node[5] is not None else ""
+        tol = f" TOLERANCE {node[9]!r}" if node[9] is not None else ""
+        return (f"{pad}ASOF JOIN {node[7].upper()} ON {node[3]} = {node[4]}{by}{tol}\n"
+                + _explain(node[1], depth + 1) + "\n" + _explain(node[2], depth + 1))
     return f"{pad}{kind.upper()} {node[2]!r}\n" + _explain(node[1], depth + 1)
 
 
@@ -2362,6 +2429,247 @@ def _join(left: DataFrame, right: DataFrame, left_on: str | tuple, right_on: str
     return DataFrame(out)
 
 
+# ------------------------------------------------------------- as-of join
+_DURATION_NS = {"ns": 1, "us": 1_000, "ms": 1_000_000, "s": 1_000_000_000, "m": 60_000_000_000,
+                "h": 3_600_000_000_000, "d": 86_400_000_000_000, "w": 604_800_000_000_000}
+
+
+def _duration_ns(s: str) -> int:
+    """A duration string of fixed-length units (ns us ms s m h d w, e.g.
+    "2h15m") in nanoseconds; the calendar units (mo q y) and the index unit (i)
+    are refused (dsl_to_ir/join.rs:337 refuses a month offset)."""
+    import re
+
+    body = s[1:] if s[:1] in "+-" else s
+    parts = re.findall(r"(\d+)(ns|us|ms|mo|s|m|h|d|w|q|y|i)", body)
+    if not parts or "".join(a + b for a, b in parts) != body:
+        raise N.InvalidOperationError(f"join_asof: cannot parse the tolerance {s!r} as a duration string")
+    total = 0
+    for num, unit in parts:
+        if unit not in _DURATION_NS:
+            raise N.ComputeError(f"join_asof: the tolerance {s!r} uses the unit '{unit}': only ns us ms s m h d w "
+                                 "have a fixed length (cannot use month offset in timedelta of an asof join; "
+                                 "consider using 4 weeks)")
+        total += int(num) * _DURATION_NS[unit]
+    return -total if s[:1] == "-" else total
+
+
+def _asof_tolerance(tolerance: Any, key: "Series") -> tuple[int, int, float]:
+    """(has_tolerance, tolerance_bits, tolerance_f64) of plgpu_join_asof for a
+    key column: a number in the key's physical unit, or for temporal keys a
+    timedelta / duration string converted to the column's unit (truncated, as
+    Duration::duration_us and friends do).  A value that does not fit the
+    key's physical type raises."""
+    import datetime as _dt
+
+    if tolerance is None:
+        return 0, 0, 0.0
+    lg, phys = key._logical_dtype(), _BY_CODE[key._col.dtype]
+    if isinstance(tolerance, (str, _dt.timedelta)):
+        if lg is None:
+            raise N.InvalidOperationError(
+                "can only use timedelta string language with Date/Datetime/Duration dtypes in join_asof")
+        if isinstance(tolerance, str):
+            ns = _duration_ns(tolerance)
+        else:
+            ns = ((tolerance.days * 86400 + tolerance.seconds) * 1_000_000 + tolerance.microseconds) * 1000
+        per = 86_400_000_000_000 if lg is Date else _DURATION_NS[lg.time_unit]
+        tolerance = builtins.abs(ns) // per * (-1 if ns < 0 else 1)
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+        raise TypeError(f"join_asof: `tolerance` must be a number, a timedelta or a duration string, "
+                        f"got {type(tolerance).__name__!r}")
+    if phys in FLOAT_DTYPES:
+        return 1, 0, float(tolerance)
+    if isinstance(tolerance, (float, np.floating)) and not np.isfinite(tolerance):
+        raise N.ComputeError(f"join_asof: the tolerance {tolerance!r} does not fit the key dtype {phys}")
+    t = int(tolerance)  # toward zero, as NumCast does
+    info = np.iinfo(phys.np_dtype)
+    if not info.min <= t <= info.max:
+        raise N.ComputeError(f"join_asof: the tolerance {tolerance!r} does not fit the key dtype {phys}")
+    return 1, (t - (1 << 64) if t >= 1 << 63 else t), 0.0
+
+
+def _null_free(s: "Series") -> "Series":
+    """The same buffers as a column without a validity buffer, for a column
+    known to hold no null."""
+    v = Series.__new__(Series)
+    v.name, v._logical = s.name, s._logical_dtype()
+    c = N.Column.from_buffer_copy(s._col)
+    c.validity, c.null_count, c.release, c.private_data = None, 0, None, None
+    v._col = c
+    v._keep = [s]
+    return v
+
+
+def _row_ids(like: "Series") -> "Series":
+    """0, 1, ... as a UInt32 column as long as `like` (the running count of a
+    null-free column, shifted by one row)."""
+    return _null_free(_null_free(like._physical_view())._cum("count")._lag("shift", 1, 0))
+
+
+def _asof_on(df: DataFrame, name: str, tolerance: Any) -> "Series":
+    if name not in df._cols:
+        raise N.ComputeError(f'unable to find column "{name}"; valid columns: {df.columns}')
+    s = df._cols[name]
+    if s.dtype in (Boolean, String):
+        if tolerance is not None:
+            raise N.InvalidOperationError("asof join with tolerance is only supported on numeric/temporal keys")
+        raise N.InvalidOperationError(
+            f"join_asof on a {'Categorical' if s._cat_codes() is not None else s.dtype} key is not supported "
+            "on the GPU executor (numeric and temporal keys only)")
+    return s
+
+
+def _asof_by_keys(df: DataFrame, names: Sequence[str]) -> list:
+    """The `by` columns as integer / float key columns both sides agree on: a
+    String or Categorical column as its short-string codes (equal strings get
+    equal codes whatever the dictionary), small integers as Int32, UInt64 on
+    its bits, logical types as their physical integers."""
+    out = []
+    for nm in names:
+        if nm not in df._cols:
+            raise N.ComputeError(f'unable to find column "{nm}"; valid columns: {df.columns}')
+        s = df._cols[nm]
+        if s.dtype is String:
+            codes, short = N.Column(), C.c_int32(0)
+            N.check(N.lib().plgpu_str_encode_short(C.byref(s._col), C.byref(codes), C.byref(short), None))
+            enc = Series._from_native(nm, codes)
+            if not short.value:
+                raise N.InvalidOperationError(
+                    f'join_asof by "{nm}": String keys longer than 7 bytes are not supported on the GPU executor')
+            s = enc
+        else:
+            s = s._physical_view()
+            phys = _BY_CODE[s._col.dtype]
+            if phys in (Int8, Int16, UInt8, UInt16):
+                s = s._cast_to(Int32)
+            elif phys is UInt64:
+                s = s._reinterpret(Int64)
+            elif phys is Float32:
+                raise N.InvalidOperationError(f'join_asof by "{nm}": Float32 keys are not supported on the GPU executor')
+        out.append(s.alias(nm))
+    return out
+
+
+def _asof_ranges(lkeys: list, rkeys: list, r_on: "Series", info: dict | None) -> tuple:
+    """The `by` groups as ranges of a regrouped right side: (right `on` keys
+    with every group contiguous and in its original order, lo, hi per left row,
+    the right frame's row of every regrouped position or None for the identity).
+    Composed from what exists: plgpu_filter drops the right rows with a null
+    `on` or `by` key, a stable plgpu_arg_sort_multi by the `by` keys alone
+    groups them unless they arrive grouped in sorted order,
+    plgpu_segment_starts gives one row per group, and a left join of the left
+    `by` keys against those unique groups brings every left row its group's
+    [lo, hi) (0, 0 without a group)."""
+    n_left = lkeys[0].len()
+    rrows = None
+    if builtins.any(bool(s._col.validity) for s in [r_on] + rkeys):
+        names = ["__on"] + [f"__b{i}" for i in range(builtins.len(rkeys))]
+        tmp = DataFrame([s.alias(n) for s, n in zip([r_on] + rkeys, names)])
+        pred = col(names[0]).is_not_null()
+        for n in names[1:]:
+            pred = pred & col(n).is_not_null()
+        mask = _eval(pred, tmp)
+        rrows = _row_ids(r_on).filter(mask)
+        r_on, rkeys = r_on.filter(mask), [k.filter(mask) for k in rkeys]
+    r_on, rkeys = _null_free(r_on), [_null_free(k) for k in rkeys]
+    n_r = r_on.len()
+    if n_r == 0:
+        zero = _null_free(Series.from_numpy("__lo", np.zeros(n_left, np.uint32)))
+        if info is not None:
+            info["asof_right_sorted"] = True
+        return r_on, zero, zero, rrows
+    k = builtins.len(rkeys)
+    starts, srt = _segment_starts(rkeys)
+    srt = srt and N.get_option("over_presorted") != 0
+    if info is not None:
+        info["asof_right_sorted"] = srt
+    if not srt:
+        idx = N.Column()
+        zeros = (C.c_int32 * k)(*([0] * k))
+        N.check(N.lib().plgpu_arg_sort_multi(_col_array(rkeys), k, zeros, zeros, C.byref(idx), None))
+        perm = Series._from_native("__perm", idx)
+        r_on, rkeys = _null_free(r_on.gather(perm)), [_null_free(s.gather(perm)) for s in rkeys]
+        rrows = perm if rrows is None else rrows.gather(perm)
+        starts, _ = _segment_starts(rkeys)
+    g_lo = _null_free(_row_ids(r_on).filter(starts))          # one row per group: its first position
+    g_hi = _null_free(g_lo._lag("shift", -1, n_r))            # and the next group's
+    gkeys = [_null_free(s.gather(g_lo)) for s in rkeys]
+    li, ri = N.Column(), N.Column()
+    if k == 1 and lkeys[0].dtype.physical() in INTEGER_DTYPES:
+        N.check(N.lib().plgpu_join(C.byref(lkeys[0]._col), C.byref(gkeys[0]._col), N.JOIN_HOW["left"], 0,
+                                   N.JOIN_ORDER["left"], N.JOIN_VALIDATE["m:m"], C.byref(li), C.byref(ri), None))
+    else:
+        N.check(N.lib().plgpu_join_multi(_col_array(lkeys), _col_array(gkeys), k, N.JOIN_HOW["left"], 0,
+                                         N.JOIN_ORDER["left"], N.JOIN_VALIDATE["m:m"], C.byref(li), C.byref(ri), None))
+    lidx, gidx = Series._from_native("__left_idx", li), Series._from_native("__group", ri)
+    if gidx.len() != n_left:
+        raise N.ComputeError("join_asof: the group table's keys are not unique")
+    lo = _null_free(g_lo.gather(gidx)._fill_with(0))
+    hi = _null_free(g_hi.gather(gidx)._fill_with(0))
+    return r_on, lo, hi, (None if rrows is None else _null_free(rrows))
+
+
+def _join_asof(left: DataFrame, right: DataFrame, left_on: str, right_on: str, by_left: tuple | None,
+               by_right: tuple | None, strategy: str, suffix: str, tolerance: Any, coalesce: bool, allow_eq: bool,
+               check_sortedness: bool, info: dict | None = None) -> DataFrame:
+    """As-of join on the GPU (plgpu_join_asof), materialised as the reference
+    does (asof/mod.rs:274 _join_asof, groups.rs:511 _join_asof_by): the left
+    frame as it is, then the right columns taken at the matched rows, without
+    the right `by` columns and, when coalescing equal `on` names, without the
+    right `on`; a clashing name gets `suffix` (general.rs:17 _finish_join)."""
+    import warnings
+
+    lk, rk = _asof_on(left, left_on, tolerance), _asof_on(right, right_on, tolerance)
+    if lk.dtype != rk.dtype:
+        raise N.ComputeError(f"mismatching key dtypes in asof-join: `{lk.dtype}` and `{rk.dtype}`")
+    has_tol, tol_bits, tol_f = _asof_tolerance(tolerance, lk)
+    l_on, r_on = lk._physical_view(), rk._physical_view()
+    if _BY_CODE[l_on._col.dtype] in (Int8, Int16, UInt8, UInt16):  # asof/mod.rs:352
+        l_on, r_on = l_on._cast_to(Int32), r_on._cast_to(Int32)
+    lo = hi = rrows = None
+    if by_left is not None:
+        for a, b in zip(by_left, by_right):
+            for df, nm in ((left, a), (right, b)):
+                if nm not in df._cols:
+                    raise N.ComputeError(f'unable to find column "{nm}"; valid columns: {df.columns}')
+            if left._cols[a].dtype != right._cols[b].dtype:
+                raise N.ComputeError(f"mismatching dtypes in 'by' parameter of asof-join: "
+                                     f"`{left._cols[a].dtype}` and `{right._cols[b].dtype}`")
+        if check_sortedness:
+            warnings.warn("Sortedness of columns cannot be checked when 'by' groups provided", UserWarning,
+                          stacklevel=2)
+        r_on, lo, hi, rrows = _asof_ranges(_asof_by_keys(left, by_left), _asof_by_keys(right, by_right), r_on, info)
+    elif check_sortedness:
+        for s in (l_on, r_on):
+            asc, nf = C.c_int32(0), C.c_int32(0)
+            N.check(N.lib().plgpu_is_sorted_asc(C.byref(s._col), C.byref(asc), C.byref(nf), None))
+            if not (asc.value and nf.value):
+                raise N.InvalidOperationError("argument in operation 'asof_join' is not sorted, please sort the "
+                                              "'expr/series/column' first")
+    out_idx, path = N.Column(), C.c_int32(0)
+    N.check(N.lib().plgpu_join_asof(
+        C.byref(l_on._col), C.byref(r_on._col), None if lo is None else C.byref(lo._col),
+        None if hi is None else C.byref(hi._col), None if rrows is None else C.byref(rrows._col),
+        N.ASOF[strategy], int(allow_eq), has_tol, tol_bits, tol_f, C.byref(out_idx), C.byref(path), None))
+    ridx = Series._from_native("__right_idx", out_idx)
+    if info is not None:
+        info["asof_path"] = N.ASOF_PATH[path.value]
+    drop = builtins.set(by_right or ())
+    if coalesce and left_on == right_on:
+        drop.add(right_on)
+    rnames = [n for n in right.columns if n not in drop]
+    out = [left._cols[n].alias(n) for n in left.columns]
+    if rnames:
+        got = (N.Column * builtins.len(rnames))()
+        N.check(N.lib().plgpu_gather(_col_array([right._cols[n] for n in rnames]), builtins.len(rnames),
+                                     C.byref(ridx._col), got, None))
+        for i, n in enumerate(rnames):
+            out.append(Series._from_native(n + suffix if n in left._cols else n, got[i],
+                                           right._cols[n]._logical_dtype()))
+    return DataFrame(out)
+
+
 def _sort(df: DataFrame, by: str | tuple, descending: bool | tuple, nulls_last: bool | tuple) -> DataFrame:
     names = _gb_keys(by)
     for nm in names:
@@ -2391,6 +2699,8 @@ def _execute(node: tuple, info: dict | None = None) -> DataFrame:
         return node[1]
     if kind == "join":
         return _join(_execute(node[1], info), _execute(node[2], info), *node[3:])
+    if kind == "join_asof":
+        return _join_asof(_execute(node[1], info), _execute(node[2], info), *node[3:], info=info)
     if kind == "sort":
         return _sort(_execute(node[1], info), node[2], node[3], node[4])
     if kind == "filter":
