@@ -954,6 +954,57 @@ int plgpu_ewm_mean(const plgpu_column* values, const plgpu_column* seg_starts /*
                    double alpha, int32_t adjust, int32_t ignore_nulls, int64_t min_samples,
                    plgpu_column* out, void* stream);
 
+/* ---- rank -------------------------------------------------------------------------
+ * plgpu_rank: the ranks of a column from its stable sort, for the whole column
+ * or per segment.  The caller has sorted (plgpu_arg_sort / plgpu_arg_sort_multi,
+ * which break ties in row order whatever `descending` says, as the reference's
+ * stable sort_by does), gathered, and marked the runs (plgpu_segment_starts:
+ * TotalEq, so -0.0 ties with 0.0 and NaN with NaN; a null equals a null).
+ * Replaces polars-ops/src/series/ops/rank.rs:68 rank (:32 rank_impl and its
+ * flush closures) and, with seg_starts, its evaluation on every group's rows
+ * (polars-expr/src/expressions/window.rs:356, GroupsToRows).
+ *   sorted_idx     null-free UInt32 permutation of 0..n-1: sorted row j is row
+ *                  sorted_idx[j] of `values`.
+ *   sorted_values  the ranked column gathered through sorted_idx.  Only its
+ *                  validity is read; within every segment its nulls are last.
+ *   tie_starts     null-free Boolean, n rows: sorted row j begins a run of equal
+ *                  (keys, value).
+ *   seg_starts     NULL: one segment; else null-free Boolean, n rows, as
+ *                  plgpu_segment_starts writes it for the keys.  Row 0 starts a
+ *                  segment and every segment start is a tie start, whatever the
+ *                  two bitmaps say (they are ORed on the device).
+ *   values         the ranked column in row order: only its validity is read,
+ *                  and becomes the output's (realigned to offset 0; no validity
+ *                  buffer when `values` has none).
+ * For sorted row j with s the last segment start <= j, a the last tie start
+ * <= j and b the next tie start > j (n when there is none):
+ *   ORDINAL j - s + 1     MIN a - s + 1     MAX b - s
+ *   AVERAGE 0.5 * ((double)min + (double)max)   (rank.rs:154)
+ *   DENSE   the number of tie starts in [s, j]
+ * written at out[sorted_idx[j]]: the output is in row order.  Sorted rows
+ * whose sorted_values bit is clear write nothing; the value buffer is zeroed
+ * first when there are any, so a null row's bytes are defined.  Nulls being
+ * last in their segment, a non-null row's rank counts non-null rows only.
+ * UInt32 output (the reference's IdxSize), Float64 for AVERAGE.
+ * Every input may be sliced and its bitmap unaligned.
+ * PLGPU_ERR_INVALID: a NULL argument (seg_starts apart), an unknown method,
+ * lengths that differ, a sorted_idx that is not a null-free UInt32 column, a
+ * tie_starts / seg_starts that is not a null-free Boolean column, more than
+ * 2^32 - 1 rows; all before any device work.  n == 0 is legal.
+ * Three launches over the bitmaps and one pass over sorted_idx (bitmap reduce
+ * per tile, scan of the tile summaries in both directions, apply with the
+ * scatter); no workgroup waits on another. */
+enum plgpu_rank_method {
+    PLGPU_RANK_AVERAGE = 1,
+    PLGPU_RANK_MIN = 2,
+    PLGPU_RANK_MAX = 3,
+    PLGPU_RANK_DENSE = 4,
+    PLGPU_RANK_ORDINAL = 5
+};
+int plgpu_rank(const plgpu_column* sorted_idx, const plgpu_column* sorted_values, const plgpu_column* tie_starts,
+               const plgpu_column* seg_starts /* NULL: one segment */, const plgpu_column* values, int32_t method,
+               plgpu_column* out, void* stream);
+
 /* ---- as-of join -----------------------------------------------------------------
  * plgpu_join_asof: for every left row the row of the right side whose `on` key
  * is the closest at or before (BACKWARD), at or after (FORWARD) or on either

@@ -213,6 +213,7 @@ SIGNATURES = {
     "plgpu_lag": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _COLP, _P]),
     "plgpu_fill": (C.c_int, [_COLP, _COLP, C.c_int32, C.c_int64, _COLP, _P]),
     "plgpu_ewm_mean": (C.c_int, [_COLP, _COLP, C.c_double, C.c_int32, C.c_int32, C.c_int64, _COLP, _P]),
+    "plgpu_rank": (C.c_int, [_COLP, _COLP, _COLP, _COLP, _COLP, C.c_int32, _COLP, _P]),
     "plgpu_join_asof": (C.c_int, [_COLP, _COLP, _COLP, _COLP, _COLP, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                   C.c_double, _COLP, C.POINTER(C.c_int32), _P]),
     "plgpu_is_sorted_asc": (C.c_int, [_COLP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
@@ -226,12 +227,13 @@ ROLLING = {"sum": 1, "mean": 2, "min": 3, "max": 4, "var": 5, "std": 6}
 CUM = {"sum": 1, "min": 2, "max": 3, "count": 4}
 LAG = {"shift": 1, "diff": 2}
 FILL = {"forward": 1, "backward": 2}
+RANK = {"average": 1, "min": 2, "max": 3, "dense": 4, "ordinal": 5}
 ASOF = {"backward": 0, "forward": 1, "nearest": 2}
 ASOF_PATH = {1: "staged", 2: "global", 3: "ranged"}  # plgpu_join_asof's *out_path
 # The geometry of the as-of join's window search (csrc/asof.hip)
 ASOF_TILE_ROWS = 2048       # kAsofTile: left rows per workgroup
 ASOF_LDS_VALUES = 2048      # kAsofLds: the largest window of right values a tile stages in LDS
-# The tile geometry of the segmented scans (csrc/seg_scan.hpp; cumulative, fill and ewm share it)
+# The tile geometry of the segmented scans (csrc/seg_scan.hpp; cumulative, fill, ewm and rank share it)
 CUM_BLOCK = 2048            # kTileBlock: rows of one workgroup scan
 CUM_TILE = 8 * CUM_BLOCK    # kTileRows: rows per workgroup of the scan kernels (one summary / carry each)
 CUM_THREADS = 256           # kTileThreads: threads of a tile's workgroup (CUM_BLOCK / 256 rows each)

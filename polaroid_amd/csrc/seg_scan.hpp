@@ -1,8 +1,8 @@
-// The core shared by the segmented scans (cumulative.hip, fill.hip, ewm.hip):
+// The core shared by the segmented scans (cumulative.hip, fill.hip, ewm.hip, rank.hip):
 // the tile geometry, the segmented workgroup scan over an operator type, the
 // totals launch's split of the tiles, the 16-byte load of a thread's rows, and
 // the bitmap words and row codes of the scans that run over validity and
-// segment-start bitmaps (fill.hip, ewm.hip).  Primitives only: each operator
+// segment-start bitmaps (fill.hip, ewm.hip, rank.hip).  Primitives only: each operator
 // keeps its own reduce / totals / apply kernels, and the tails of the apply
 // kernels stay written out there (profiles/seg_scan_isa.md says why).
 #pragma once

@@ -23,7 +23,7 @@ class Expr:
 
     def __init__(self, kind: str, args: Sequence["Expr"] = (), op: str | None = None,
                  value: Any = None, name: str | None = None):
-        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | fill | ewm | over | ...
+        self.kind = kind          # col | lit | bin | un | agg | alias | len | rolling | cum | lag | fill | ewm | rank | over | ...
         self.args = tuple(args)
         self.op = op
         self.value = value
@@ -82,6 +82,8 @@ class Expr:
             alpha, adjust, min_samples, ignore_nulls = self.value
             return (f"{self.args[0]!r}.ewm_{self.op}(alpha={alpha!r}, adjust={adjust}, min_samples={min_samples}, "
                     f"ignore_nulls={ignore_nulls})")
+        if self.kind == "rank":
+            return f"{self.args[0]!r}.rank(method={self.op!r}, descending={self.value[0]})"
         if self.kind == "over":
             keys = ", ".join(f'col("{k}")' for k in self.value)
             return f"{self.args[0]!r}.over([{keys}])"
@@ -231,8 +233,8 @@ class Expr:
                 "on the GPU executor")
         if _has_scan(self):
             raise N.InvalidOperationError(
-                f"{self!r}.{op}(): a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / "
-                "backward_fill / fill_null(strategy=...) / ewm_mean) inside an aggregation's input is not supported "
+                f"{self!r}.{op}(): a cumulative, lag, fill, ewm or rank function (cum_* / shift / diff / forward_fill / "
+                "backward_fill / fill_null(strategy=...) / ewm_mean / rank) inside an aggregation's input is not supported "
                 "on the GPU executor: it gives one value per row, in row order")
         return Expr("agg", (self,), op=op, value=value)
 
@@ -329,6 +331,14 @@ class Expr:
         return Expr("ewm", (self,), op="mean", value=(a, bool(adjust), _ewm_min_samples(min_samples),
                                                       bool(ignore_nulls)))
 
+    def rank(self, method: str = "average", *, descending: bool = False, seed: int | None = None) -> "Expr":
+        """Expr.rank (polars-ops/src/series/ops/rank.rs:68): average / min /
+        max / dense / ordinal; nulls stay null and are not counted.  UInt32,
+        Float64 for "average"."""
+        _rank_method(method)
+        _lag_input(self, "rank")
+        return Expr("rank", (self,), op=method, value=(bool(descending),))
+
     def ewm_std(self, *args: Any, **kwargs: Any) -> "Expr":
         raise N.InvalidOperationError(
             "ewm_std is not built on the GPU executor (only ewm_mean is; the variance carries a different state)")
@@ -351,7 +361,8 @@ class Expr:
         min / max / count / len / first / last / std / var of an elementwise
         expression (or pl.len()), and `<elementwise>.cum_*()` / `.shift(...)` /
         `.diff(...)` / `.forward_fill(...)` / `.backward_fill(...)` /
-        `.fill_null(strategy=...)` / `.ewm_mean(...)`, over plain key columns."""
+        `.fill_null(strategy=...)` / `.ewm_mean(...)` / `.rank(...)`, over
+        plain key columns."""
         keys: list[str] = []
         items = [partition_by, *more_exprs]
         while items:
@@ -392,7 +403,12 @@ class Expr:
                 f"{self!r}.over(...): the GPU executor evaluates over groups only rolling_* functions and the "
                 f"aggregations {', '.join(_OVER_AGGS)} (or len()) of an elementwise expression, "
                 "and cum_sum / cum_min / cum_max / cum_count / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...) / ewm_mean of an elementwise expression")
+                "fill_null(strategy=...) / ewm_mean / rank of an elementwise expression")
+        if f.kind == "rank" and builtins.len(keys) >= N.MAX_KEYS:
+            raise N.InvalidOperationError(
+                f"{self!r}.over(...): rank over {builtins.len(keys)} partition keys is not supported on the GPU "
+                f"executor: the sort takes {N.MAX_KEYS} columns and the ranked value is one of them, so rank "
+                f"partitions by at most {N.MAX_KEYS - 1} keys")
         return Expr("over", (self,), op="over", value=tuple(keys))
 
     def sort(self, *, descending: bool = False, nulls_last: bool = False) -> "Expr":
@@ -416,7 +432,7 @@ def _rolling(e: Expr, kind: str, window_size: int, weights, min_samples, center,
 
 
 def _is_rowwise(e: Expr) -> bool:
-    """Elementwise expressions and rolling / cumulative / lag / fill / ewm functions of
+    """Elementwise expressions and rolling / cumulative / lag / fill / ewm / rank functions of
     them: one value per row, in row order."""
     if e.kind == "over":
         return True
@@ -541,6 +557,22 @@ def _prepare_alpha(com: Any = None, span: Any = None, half_life: Any = None, alp
     return float(alpha)
 
 
+_RANK_METHODS = ("average", "min", "max", "dense", "ordinal")
+
+
+def _rank_method(method: Any) -> str:
+    """The tie method of rank: "random" is refused by name (it would need the
+    reference's RNG stream), anything else unknown is a ValueError."""
+    if method == "random":
+        raise N.InvalidOperationError(
+            "rank(method='random') is not supported on the GPU executor: its tie order comes from the "
+            "reference's random number stream (with or without `seed`)")
+    if method not in _RANK_METHODS:
+        raise ValueError(f"rank: `method` must be one of {', '.join(map(repr, _RANK_METHODS))} (or 'random'), "
+                         f"got {method!r}")
+    return method
+
+
 def _ewm_min_samples(v: Any) -> int:
     import operator
 
@@ -556,7 +588,8 @@ def _ewm_min_samples(v: Any) -> int:
 
 
 _OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")
-_SCAN_KINDS = ("cum", "lag", "fill", "ewm")  # the segmented scans (frame._window_fn; csrc/seg_scan.hpp)
+# the segmented scans (frame._window_fn; csrc/seg_scan.hpp); rank follows their rules everywhere
+_SCAN_KINDS = ("cum", "lag", "fill", "ewm", "rank")
 _ELEMENTWISE = ("col", "lit", "bin", "un", "alias", "ternary", "cast", "fill_null", "strfn", "over")
 
 

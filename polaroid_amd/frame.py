@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _native as N
 from .expr import (_SCAN_KINDS, Expr, _ewm_min_samples, _fill_args, _fill_limit, _has_over, _has_scan, _lag_n,
-                   _prepare_alpha, col, lit, lower, to_instr_array)
+                   _prepare_alpha, _rank_method, col, lit, lower, to_instr_array)
 
 
 # ------------------------------------------------------------------ dtypes
@@ -841,6 +841,62 @@ class Series:
         return self._ewm_mean(_prepare_alpha(com, span, half_life, alpha), adjust, _ewm_min_samples(min_samples),
                               ignore_nulls)
 
+    # rank (Series.rank) --------------------------------------------------------
+    def _rank(self, method: str, descending: bool = False, keys: "Sequence[Series] | None" = None) -> "Series":
+        """Ranks on the device (rank.rs:68): a stable sort with the nulls
+        last, the sorted rows' runs of equal values (plgpu_segment_starts:
+        TotalEq), then plgpu_rank, which writes in row order.  `keys`
+        (Expr.over, as _over_sort_keys gives them): the sort is by the keys
+        first and the ranks restart at every new key tuple.  The dtypes are
+        those the sort takes; Int8 / Int16 / UInt8 / UInt16 rank as Int64 and
+        Float32 as Float64 (both casts keep order and equality), temporal
+        types on their physical integers.  UInt32, Float64 for "average"."""
+        method = _rank_method(method)
+        if self._cat_codes() is not None or self.dtype is String:
+            raise N.InvalidOperationError(
+                f"rank of a {self.dtype} column is not supported on the GPU executor (String / Categorical "
+                "values have no device sort order here)")
+        phys = _BY_CODE[self._col.dtype]
+        if phys in (Int8, Int16, UInt8, UInt16):
+            src = self._physical_view()._cast_to(Int64)
+        elif phys is Float32:
+            src = self._cast_to(Float64)
+        elif phys in (Boolean, Int32, Int64, UInt32, Float64):
+            src = self._physical_view()
+        else:
+            raise N.InvalidOperationError(
+                f"rank of a {self.dtype} column is not supported on the GPU executor (the sort takes Boolean, "
+                "Int32, Int64, UInt32 and Float64 keys)")
+        cols = list(keys or []) + [src]
+        k = builtins.len(cols)
+        if k > N.MAX_KEYS:
+            raise N.InvalidOperationError(
+                f"rank over {k - 1} partition keys is not supported on the GPU executor: the sort takes "
+                f"{N.MAX_KEYS} columns and the ranked value is one of them")
+        if builtins.any(c.len() != src.len() for c in cols):
+            raise N.ShapeError("over(): the partition keys and the values differ in length")
+        idx = N.Column()
+        if k == 1 and phys is not Boolean:
+            N.check(N.lib().plgpu_arg_sort(C.byref(src._col), int(bool(descending)), 1, C.byref(idx), None))
+        else:  # keys ascending with their nulls first; the value with `descending`, its nulls last
+            desc = (C.c_int32 * k)(*([0] * (k - 1) + [int(bool(descending))]))
+            last = (C.c_int32 * k)(*([0] * (k - 1) + [1]))
+            N.check(N.lib().plgpu_arg_sort_multi(_col_array(cols), k, desc, last, C.byref(idx), None))
+        idx_s = Series._from_native("__idx", idx)
+        got = (N.Column * k)()
+        N.check(N.lib().plgpu_gather(_col_array(cols), k, C.byref(idx_s._col), got, None))
+        srt = [Series._from_native(c.name, got[i]) for i, c in enumerate(cols)]
+        ties, _ = _segment_starts(srt)
+        seg = _segment_starts(srt[:-1])[0] if k > 1 else None
+        out = N.Column()
+        N.check(N.lib().plgpu_rank(C.byref(idx_s._col), C.byref(srt[-1]._col), C.byref(ties._col),
+                                   None if seg is None else C.byref(seg._col), C.byref(src._col), N.RANK[method],
+                                   C.byref(out), None))
+        return Series._from_native(self.name, out)
+
+    def rank(self, method: str = "average", *, descending: bool = False, seed: int | None = None) -> "Series":
+        return self._rank(method, descending)
+
     def _physical_view(self) -> "Series":
         """This column without its logical dtype (the same buffers)."""
         s = self.alias(self.name)
@@ -1236,8 +1292,8 @@ class LazyFrame:
                 "compute it with with_columns first and filter on that column")
         if _has_scan(pred):
             raise N.InvalidOperationError(
-                "a cumulative, lag, fill or ewm function (cum_* / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...) / ewm_mean) in a filter predicate is not supported on the GPU executor: compute it "
+                "a cumulative, lag, fill, ewm or rank function (cum_* / shift / diff / forward_fill / backward_fill / "
+                "fill_null(strategy=...) / ewm_mean / rank) in a filter predicate is not supported on the GPU executor: compute it "
                 "with with_columns first and filter on that column")
         return LazyFrame(("filter", self._node, pred))
 
@@ -1763,6 +1819,8 @@ def _window_fn(f: Expr, vals: Series, seg: Series | None = None) -> Series:
         return vals._cum(f.op, f.value[0], seg=seg)
     if f.kind == "ewm":
         return vals._ewm_mean(*f.value, seg=seg)
+    if f.kind == "rank":  # (over groups: _over_window's own branch, it sorts by the value too)
+        return vals._rank(f.op, f.value[0])
     if f.kind == "fill":
         if f.op in ("forward", "backward"):
             return vals._fill(f.op, f.value[0], seg=seg)
@@ -1778,8 +1836,15 @@ def _over_window(f: Expr, keys: Sequence[str], df: DataFrame, cache: dict | None
     on the gathered rows, and a gather back through the inverse permutation
     (window.rs:524 MapStrategy::Map).  fill_null(strategy = zero / one) is the
     plain fill; min / max / mean fill with the group's aggregate (_over_agg)
-    through the elementwise fill_null."""
+    through the elementwise fill_null.  rank(...).over(keys) sorts by the
+    keys and the value together (Series._rank) and shares nothing with the
+    others: plgpu_rank writes in row order, so no inverse permutation and no
+    gather back."""
     vals = _eval(f.args[0], df, cache)
+    if f.kind == "rank":
+        if vals.len() != df.height:
+            raise N.ShapeError("over(): the partition keys and the values differ in length")
+        return vals._rank(f.op, f.value[0], keys=_over_sort_keys(df, keys))
     if f.kind == "fill" and f.op not in ("forward", "backward"):
         if f.op in ("zero", "one") or vals.dtype is String or vals._col.dtype == N.BOOL \
                 or (f.op == "mean" and vals._logical_dtype() is not None) or not vals._col.validity:
@@ -2037,7 +2102,7 @@ def _gb_lower(df: DataFrame, key: str | tuple | None, aggs: list[Expr], pred: Ex
         elif base.kind in _SCAN_KINDS:
             raise N.InvalidOperationError(
                 f"{e!r} is not an aggregation: cum_* / shift / diff / forward_fill / backward_fill / "
-                "fill_null(strategy=...) / ewm_mean give one value per row and are not supported inside group_by().agg() on "
+                "fill_null(strategy=...) / ewm_mean / rank give one value per row and are not supported inside group_by().agg() on "
                 "the GPU executor (use .over(keys) in with_columns)")
         else:
             raise N.InvalidOperationError(
