@@ -321,7 +321,10 @@ int plgpu_get_option(const char* name, int64_t* out);
 /* Kernel timer (option "ktime" = 1): HIP-event times of the library's named
  * kernels since the last reset, one "name\tms_total\tlaunches\n" line per
  * kernel into buf (NUL-terminated); waits for pending launches.  reset != 0
- * clears the sums.  Measurement support (no reference counterpart; the
+ * clears the sums.  A launch that an A/B option selects or shapes carries a
+ * name of its own (rl_stream_kernel, srt_downsweep_w4_kernel,
+ * gb_part_agg_rows4_kernel, ...), so a test can tell that it ran; the default
+ * configuration's names do not change.  Measurement support (no reference counterpart; the
  * reference's equivalent is its profiling via `should_time`,
  * crates/polars-mem-engine/src/executors/scan/python_scan.rs:91). */
 int plgpu_ktime_read(char* buf, int64_t cap, int32_t reset);

@@ -533,7 +533,8 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
             const plgpu_column& pc = cols[dp.simple_col];
             const uint64_t* pcol = (const uint64_t*)pc.values + pc.offset;
             if (e == hipSuccess) {
-                KtScope kt("filter_fused8_kernel", s);
+                // (option filt_pipe 0: a timer name of its own, the tests' proof that it ran)
+                KtScope kt(options().filt_pipe != 0 ? "filter_fused8_kernel" : "filter_fused8_nopipe_kernel", s);
                 if (options().filt_pipe != 0)
                     filter_fused8_kernel<true><<<(unsigned)ntiles, kFilterThreads, 0, s>>>(
                         sa, pcol, dp.simple_col, dp, n, status, (uint32_t*)(status + ntiles));
@@ -618,7 +619,7 @@ static int run_filter(const plgpu_column* cols, int32_t ncols, int src, const De
         ++sa.ncols;
     }
     if (!rc && sa.ncols > 0 && total > 0) {
-        KtScope kt("filter_scatter8_kernel", s);
+        KtScope kt(options().filt_pipe != 0 ? "filter_scatter8_kernel" : "filter_scatter8_nopipe_kernel", s);
         if (options().filt_pipe != 0)
             filter_scatter8_kernel<true><<<grid_for(ntiles, 1, 256 * 8), kFilterThreads, 0, s>>>(sa, n, ntiles,
                                                                                                mask_words, offs);

@@ -2930,7 +2930,10 @@ static int gb_main(GbRun& R, bool auto_refit, bool* refit, int32_t* hint) {
         for (int a = 0; a < kMaxAcc; ++a) p.bottom[a] = R.hb[a];
         PLGPU_HIP(hipEventRecord(ev0, R.s));
         if (n > 0 && R.part) {
-            KtScope kt("gb_part_agg_kernel", R.s);
+            // (one-workgroup partitions kept off their table regions by option
+            // part_direct 0: a timer name of their own, the tests' proof)
+            KtScope kt(R.part_blocks == 1 && options().part_direct == 0 ? "gb_part_agg_nodirect_kernel"
+                                                                        : "gb_part_agg_kernel", R.s);
             PLGPU_HIP(launch_partitioned(R));
         } else if (n > 0) {
             // the fused kernel covers every row (its last tile masked); off

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -2009,7 +2010,8 @@ hipError_t launch_fast_rows(const Plan& pl, const DevProgram& dp, hipStream_t s)
         const int64_t nall = q.n_full / tile + (pl.p.n > q.n_full ? 1 : 0);
         q.tiles_per_wg = (int32_t)((nall + grid - 1) / grid);
     }
-    KtScope kt("gb_fast_kernel", s);
+    // (option wave_report: a timer name of its own, the tests' proof that it ran)
+    KtScope kt(q.wave_report ? "gb_fast_wave_report_kernel" : "gb_fast_kernel", s);
     gb_fast_kernel<NACC, PRED, SUMONLY, ROWS, LIMBS, RUNS, false, DERIV, VAR, PACK, NULLS>
         <<<grid, kGbThreads, lds, s>>>(q, dp);
     return hipGetLastError();
@@ -2150,9 +2152,15 @@ hipError_t launch_part_fast(const Plan& pp, int grid, hipStream_t s) {
     // with ~17k rows per partition (1e7 groups) 512 (7.7 against 13.7 ms)
     const int64_t per_wg = pp.p.n / std::max(grid, 1);
     int threads = RACC || per_wg < 65536 ? kGbThreads : kGbPartThreads;
-    if (!RACC && options().part_threads > 0) threads = std::min(kGbPartThreads, options().part_threads);
+    const bool forced = !RACC && options().part_threads > 0;
+    if (forced) threads = std::min(kGbPartThreads, options().part_threads);
     GbParams q = pp.p;
     q.wave_report = options().wave_report;
+    // (inside the caller's gb_part_agg_kernel scope: a timer name of their own
+    // for the launches an option shapes, the tests' proof that they ran)
+    const char* forced_name = threads == kGbPartThreads ? "gb_part_agg_t1024_kernel"
+                              : threads == kGbThreads   ? "gb_part_agg_t512_kernel"
+                                                        : "gb_part_agg_tn_kernel";
     if constexpr (LIMBS == 2 && !RACC) {
         // option part_rows4 (A/B): 512-thread workgroups holding 4 rows per
         // thread (two row pairs in flight per tile instead of one), compiled
@@ -2165,10 +2173,13 @@ hipError_t launch_part_fast(const Plan& pp, int grid, hipStream_t s) {
                 (void)hipFuncSetAttribute(k4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 attr4 = true;
             }
+            KtScope kt("gb_part_agg_rows4_kernel", s);
             gb_fast_kernel<NACC, 0, true, 4, 2, false, true, false, 0, 0, NULLS><<<grid, threads, lds, s>>>(q, none);
             return hipGetLastError();
         }
     }
+    std::optional<KtScope> kt;
+    if (forced || q.wave_report) kt.emplace(forced ? forced_name : "gb_part_agg_wave_report_kernel", s);
     gb_fast_kernel<NACC, 0, true, 2, LIMBS, RACC, true, false, 0, 0, NULLS><<<grid, threads, lds, s>>>(q, none);
     return hipGetLastError();
 }

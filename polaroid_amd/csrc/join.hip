@@ -2016,7 +2016,9 @@ static int jn_radix_take(const plgpu_column* left_key, const plgpu_column* right
     if (!rc) {
         rj_init_kernel<<<(unsigned)std::min<int64_t>((ncells + 255) / 256, cus * 16), 256, 0, s>>>(cells, ncells);
         if (nb > 0) {
-            KtScope kt("rj_build_kernel", s);
+            // (sub-tables sized for another load than 35 %, option
+            // join_radix_load: a timer name of its own, the tests' proof)
+            KtScope kt(load != 35 ? "rj_build_load_kernel" : "rj_build_kernel", s);
             rj_build_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((nb + 255) / 256, cus * 16)), 256, 0,
                               s>>>(bk, bp, nb, cells, nbk, pbits, status);
         }

@@ -1873,10 +1873,26 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
     if (window_size <= kRwMaxW) {
         const unsigned g = (unsigned)((p.n + (int64_t)kRwOut * kRwWaves - 1) / ((int64_t)kRwOut * kRwWaves));
         const bool nl = p.c.validity != nullptr;
-        KtScope kt(seg ? (var ? "rl_wave_var_seg_kernel" : "rl_wave_seg_kernel")
-                       : (var ? "rl_wave_var_kernel" : "rl_wave_kernel"), s);
         const bool hot = var && !nl && !p.var_f32 && options().rl_var_hot && p.full && p.fast_div && p.var128;
         const bool mhot = !var && !nl && !p.out_int && options().rl_mean_hot && p.full;
+        // option rl_stream: the null-free launches below that have a streamed
+        // form take it (rl_mean_hot_kernel has none); its grid from rl_grid
+        const bool streamed = !seg && !nl && !mhot && options().rl_stream != 0;
+        const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
+        const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus() * per_cu));
+        // the timer's name: the default configuration's launches keep theirs;
+        // the streamed ones ("_grid": workgroups per CU other than 4) and the
+        // ones without the one-correction quotients (option rl_div 0) carry
+        // their own, the tests' proof that they ran.  The flags that pick the
+        // name are the ones that pick the launch.
+        const bool sgrid = per_cu != 4;
+        const char* ktn = seg ? (var ? "rl_wave_var_seg_kernel" : "rl_wave_seg_kernel")
+                              : (var ? "rl_wave_var_kernel" : "rl_wave_kernel");
+        if (streamed && hot) ktn = sgrid ? "rl_var_hot_stream_grid_kernel" : "rl_var_hot_stream_kernel";
+        else if (streamed && var) ktn = sgrid ? "rl_stream_var_grid_kernel" : "rl_stream_var_kernel";
+        else if (streamed) ktn = sgrid ? "rl_stream_grid_kernel" : "rl_stream_kernel";
+        else if (!seg && !p.fast_div) ktn = var ? "rl_wave_var_nodiv_kernel" : "rl_wave_nodiv_kernel";
+        KtScope kt(ktn, s);
         if (hot || mhot) {
             // the common blocks by rl_var_hot_kernel, the rest listed for
             // rl_var_rest_kernel (stream-ordered; the count read on the device)
@@ -1888,9 +1904,6 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
                 plgpu_column_release(out);
                 return arc == PLGPU_ERR_HIP ? hip_fail(hipGetLastError(), "rolling") : arc;
             }
-            const bool st = options().rl_stream != 0;
-            const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
-            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus() * per_cu));
             const unsigned gr = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus()));
 #define PLGPU_RLHOT(DT)                                                      \
     do {                                                                     \
@@ -1899,8 +1912,8 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
             rl_var_rest_kernel<DT, false><<<gr, 64 * kRwWaves, 0, s>>>(p);   \
             break;                                                           \
         }                                                                    \
-        if (st && p.var == 2) rl_var_hot_kernel<DT, true, true><<<gs, 64 * kRwWaves, 0, s>>>(p);    \
-        else if (st) rl_var_hot_kernel<DT, true, false><<<gs, 64 * kRwWaves, 0, s>>>(p);       \
+        if (streamed && p.var == 2) rl_var_hot_kernel<DT, true, true><<<gs, 64 * kRwWaves, 0, s>>>(p);    \
+        else if (streamed) rl_var_hot_kernel<DT, true, false><<<gs, 64 * kRwWaves, 0, s>>>(p); \
         else if (p.var == 2) rl_var_hot_kernel<DT, false, true><<<g, 64 * kRwWaves, 0, s>>>(p); \
         else rl_var_hot_kernel<DT, false, false><<<g, 64 * kRwWaves, 0, s>>>(p);               \
         rl_var_rest_kernel<DT><<<gr, 64 * kRwWaves, 0, s>>>(p);              \
@@ -1917,10 +1930,8 @@ static int rolling_impl(const plgpu_column* values, const plgpu_column* seg_star
             if (values->dtype == PLGPU_F64) rl_launch_seg<PLGPU_F64>(p, var, nl, false, false, g, 1, s);
             else if (values->dtype == PLGPU_I64) rl_launch_seg<PLGPU_I64>(p, var, nl, false, false, g, 1, s);
             else rl_launch_seg<PLGPU_I32>(p, var, nl, false, false, g, 1, s);
-        } else if (!nl && options().rl_stream != 0) {
+        } else if (streamed) {
             // null-free: resident waves streaming their blocks
-            const int per_cu = options().rl_grid > 0 ? options().rl_grid : 4;
-            const unsigned gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)g, (int64_t)num_cus() * per_cu));
             if (values->dtype == PLGPU_F64) {
                 if (var) rl_stream_kernel<PLGPU_F64, true><<<gs, 64 * kRwWaves, 0, s>>>(p);
                 else rl_stream_kernel<PLGPU_F64, false><<<gs, 64 * kRwWaves, 0, s>>>(p);

@@ -493,9 +493,12 @@ template <bool IN_P, int OUT>
 static void srt_down(const uint64_t* ki, const uint32_t* ii, int64_t nv, int shift, int64_t ntiles,
                      const uint32_t* off, uint64_t* ko, uint32_t* io, int cons, uint64_t kmask, hipStream_t s) {
     // XCD-aware tiles (round-robin tiles measured slower, profiles/r02_sort_xcd_ab.log)
-    KtScope kt("srt_downsweep_kernel", s);
-    if constexpr (IN_P && OUT != SRT_SEP) {
-        if (options().srt_w4) {
+    // (the timer tells the srt_w4 launches apart: the tests' proof that they ran)
+    constexpr bool W4 = IN_P && OUT != SRT_SEP;
+    const bool w4 = W4 && options().srt_w4 != 0;
+    KtScope kt(w4 ? "srt_downsweep_w4_kernel" : "srt_downsweep_kernel", s);
+    if constexpr (W4) {
+        if (w4) {
             srt_downsweep_kernel<IN_P, OUT, 4>
                 <<<(unsigned)ntiles, kSrtThreads, 0, s>>>(ki, ii, nv, shift, ntiles, off, ko, io, cons, kmask);
             return;
@@ -550,12 +553,13 @@ static int radix_passes(DevBuf<uint64_t> keys[2], DevBuf<uint32_t> idx[2], int64
         const int shift = packed ? 32 + S - cons : S;
         const uint32_t* ii = (ids_implicit && j == 0) ? nullptr : idx[cur];
         if (!(pre && j == 0 && S == 0)) {  // byte-0 counts already in sc.cnt
-            KtScope kt("srt_upsweep_kernel", s);
-        {
             const int tpw = std::max<int>(1, (int)options().srt_up_tiles);
+            // (a timer name per srt_up_tiles value the tests set: their proof)
+            KtScope kt(tpw == 1 ? "srt_upsweep_kernel" : tpw == 2 ? "srt_upsweep_t2_kernel"
+                       : tpw == 3 ? "srt_upsweep_t3_kernel" : tpw == 8 ? "srt_upsweep_t8_kernel"
+                                                                       : "srt_upsweep_tn_kernel", s);
             srt_upsweep_kernel<<<(unsigned)((ntiles + tpw - 1) / tpw), kSrtThreads, 0, s>>>(keys[cur], nv, shift,
                                                                                            ntiles, sc.cnt, tpw);
-        }
         }
         e = scan_exclusive32_inplace(sc.cnt, ntiles * 256, sc.part, s);
         if (e != hipSuccess) return hip_fail(e, "sort scan");

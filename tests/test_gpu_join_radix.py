@@ -59,18 +59,16 @@ def _check(out, lk, rk, ncarry, lcols, pay):
         assert np.array_equal(out[f"c{j}"].to_numpy()[a], lcols[j][ol[b]]), j
 
 
-@pytest.mark.parametrize("nl,nr,keys_per,ncarry", [
+# probe rows, build rows, build keys per partition, carried left columns
+FORCED_CASES = [
     (1, 1, 0, 1), (1000, 100, 16, 1), (50_000, 20_000, 64, 1), (300_001, 60_000, 1024, 2),
     (300_001, 60_000, 32, 3),      # 2^11 partitions: two scatter levels
-    (200_000, 100_000, 512, 4), (120_000, 7, 1, 5), (4099, 3000, 100, 2)])
-@pytest.mark.parametrize("batch", [8, 4])
-def test_radix_join_forced_vs_oracle(gpu, plgpu_option, nl, nr, keys_per, ncarry, batch):
-    """Forced onto the partitioned path (join_radix = 2) with small
-    partitions; carried left columns besides the key: li plus ncarry - 1;
-    the match pass with 8 or 4 probe steps in flight."""
-    plgpu_option("join_radix", 2)
-    plgpu_option("join_radix_keys", keys_per)
-    plgpu_option("join_radix_batch", batch)
+    (200_000, 100_000, 512, 4), (120_000, 7, 1, 5), (4099, 3000, 100, 2)]
+
+
+def _forced_case(nl, nr, keys_per, ncarry):
+    """The frames of one FORCED_CASES row and their host columns:
+    (left, right, lk, rk, lcols, pay)."""
     rng = np.random.default_rng(nl + nr + keys_per)
     rk = _unique_keys(rng, nr, 4 * max(nr, 1))
     rk[0] = np.iinfo(np.int64).max
@@ -84,6 +82,19 @@ def test_radix_join_forced_vs_oracle(gpu, plgpu_option, nl, nr, keys_per, ncarry
     left = pl.DataFrame([pl.Series.from_numpy("k", lk), pl.Series.from_numpy("li", np.arange(nl, dtype=np.int64))] +
                         [pl.Series.from_numpy(f"c{j}", c) for j, c in enumerate(lcols)])
     right = pl.DataFrame([pl.Series.from_numpy("k", rk), pl.Series.from_numpy("p", pay)])
+    return left, right, lk, rk, lcols, pay
+
+
+@pytest.mark.parametrize("nl,nr,keys_per,ncarry", FORCED_CASES)
+@pytest.mark.parametrize("batch", [8, 4])
+def test_radix_join_forced_vs_oracle(gpu, plgpu_option, nl, nr, keys_per, ncarry, batch):
+    """Forced onto the partitioned path (join_radix = 2) with small
+    partitions; carried left columns besides the key: li plus ncarry - 1;
+    the match pass with 8 or 4 probe steps in flight."""
+    plgpu_option("join_radix", 2)
+    plgpu_option("join_radix_keys", keys_per)
+    plgpu_option("join_radix_batch", batch)
+    left, right, lk, rk, lcols, pay = _forced_case(nl, nr, keys_per, ncarry)
     out, names = _join(left, right)
     assert "rj_match_kernel" in names, names
     _check(out, lk, rk, len(lcols) + 1, lcols, pay)
