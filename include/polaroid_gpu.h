@@ -315,6 +315,12 @@ int plgpu_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
  *                  window of the right column its keys can touch, staged in
  *                  LDS where it fits, 2 every row searches the whole right
  *                  column (tests / A-B; results never depend on it)
+ *   "gb_claim"     fused group-by without an explicit "grid_rounds": 1 (the
+ *                  default) the resident workgroups' waves claim their rows
+ *                  chunk by chunk, 0 the static grid of several rounds (A/B)
+ *   "claim_cap_rows" rows per workgroup at which its waves stop claiming, a
+ *                  multiple of 1024 (0: the kernel's limit of 2^22; tests
+ *                  reach the cap with a small input)
  * An unknown name is PLGPU_ERR_INVALID. */
 int plgpu_set_option(const char* name, int64_t value);
 int plgpu_get_option(const char* name, int64_t* out);

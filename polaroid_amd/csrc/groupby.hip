@@ -859,7 +859,12 @@ static int32_t plan_bottom(uint64_t maxex) {
     return e - 1075 - (kSumWindowBits - 53);
 }
 
-__global__ void gb_init_table_kernel(uint64_t* gtab, int64_t words_per_field, int nfields, uint64_t min_init_mask) {
+// (also zeroes the fused kernel's claim counters, GbParams::claim: one launch
+// before every attempt)
+__global__ void gb_init_table_kernel(uint64_t* gtab, int64_t words_per_field, int nfields, uint64_t min_init_mask,
+                                     uint32_t* claim) {
+    if (blockIdx.x == 0 && claim)
+        for (int i = threadIdx.x; i < kClaimSegs * kClaimStride; i += blockDim.x) claim[i] = 0u;
     for (int f = 0; f < nfields; ++f) {
         const uint64_t v = f == 0 ? kEmptyKey : (((min_init_mask >> f) & 1ull) ? ~0ull : 0ull);
         uint64_t* q = gtab + (int64_t)f * words_per_field;
@@ -1803,6 +1808,7 @@ struct GbRun {
     DevBuf<uint64_t> status;     // ST_WORDS words + kMaxAcc int32 bottoms
     int32_t* bottoms = nullptr;  // (inside status)
     DevBuf<uint64_t> gtab;
+    DevBuf<uint32_t> claim;      // the fused kernel's claim counters (GbParams::claim)
     uint64_t st[ST_WORDS];
     int32_t hb[kMaxAcc];         // host copy of the fixed-point bottoms
     int gbits = 10;
@@ -2818,7 +2824,9 @@ static int gb_alloc_table(GbRun& R) {
     if (rc) return rc;
     p.gtab = R.gtab;
     const int ig = (int)std::min<int64_t>((int64_t)(wpf + 255) / 256, 256 * 8);
-    gb_init_table_kernel<<<ig, 256, 0, R.s>>>(R.gtab, (int64_t)wpf, p.nfields, p.min_init_mask);
+    if (R.claim == nullptr && (rc = R.claim.alloc((size_t)kClaimSegs * kClaimStride * 4, R.s))) return rc;
+    p.claim = R.claim;
+    gb_init_table_kernel<<<ig, 256, 0, R.s>>>(R.gtab, (int64_t)wpf, p.nfields, p.min_init_mask, p.claim);
     // keep the plan words (distinct / sampled), clear the run words
     PLGPU_HIP(hipMemsetAsync(R.status, 0, 6 * 8, R.s));
     PLGPU_HIP(hipMemsetAsync(R.status + ST_MAXEX, 0, (ST_WORDS - ST_MAXEX) * 8, R.s));

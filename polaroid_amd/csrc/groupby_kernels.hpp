@@ -38,10 +38,18 @@ constexpr int kLimb2Margin = 4;
 // slots over 32 bank pairs).  LDS words per slot:
 constexpr int slim_vwords(int nacc) { return (1 + 3 * nacc) | 1; }
 constexpr int slim_words(int nacc) { return 1 + slim_vwords(nacc); }
+// (the two below: the fast kernel's static grid only -- an explicit grid_rounds, gb_claim 0, the range-local mode)
 constexpr int kMinTilesPerWg = 160;  // fast kernel: fewer rounds below this many tiles per workgroup
 constexpr int kGridRounds = 8;        // fast kernel grid = rounds x resident workgroups       // binades below the smallest sampled exponent kept by 2 limbs
 constexpr int kHeadroomBinades = 8;   // above the sampled max exponent
 constexpr int64_t kMaxRowsPerWg = int64_t(1) << 22;  // keeps 40-bit limbs exact in int64
+// fast kernel, claimed rows (GbParams::claim): segments (a multiple of 8, so
+// that a segment's claimants mostly share an XCD; at most 64, one counter per
+// lane when a wave looks for work), units per claim, and the counters'
+// distance in 32-bit words (one 128-byte line each)
+constexpr int kClaimSegs = 64;
+constexpr int kClaimChunk = 8;
+constexpr int kClaimStride = 32;
 constexpr int kPlanSamples = 65536;
 constexpr int kPlanSetSlots = 4096;   // LDS hash set of the distinct-key sample (32 KiB)
 constexpr int kPlanSetWord = 32;      // the plan's global key set, in words after the status block
@@ -203,6 +211,19 @@ struct GbParams {
     // null_key (a value no non-null key holds): those rows are the null group
     int32_t has_null_key;
     int64_t null_key;
+    // fused kernel, claimed rows (launch_fast_rows; null = the grid-strided
+    // tile order): the launch's units (one wave's share of a tile, 64 x ROWS
+    // rows; claim_units of them, the masked ones after n_full included) are
+    // cut into claim_segs contiguous segments of claim_seg_units units, and
+    // segment s hands out chunks of claim_chunk units from its counter
+    // claim[s * kClaimStride].  A wave claims at most claim_cap units.
+    uint32_t* claim;
+    int32_t claim_segs;
+    int32_t claim_chunk;
+    int32_t claim_cap;
+    int32_t _pad3;
+    int64_t claim_seg_units;
+    int64_t claim_units;
 };
 
 // ------------------------------------------------------ invariant checks
@@ -998,10 +1019,12 @@ struct FastTile {
     uint32_t nr[NUL ? (ROWS + 1) / 2 : 1][NUL ? (NACC > 0 ? NACC : 1) + 2 : 1];
 };
 
-// Row j of tile t for this thread: pairs of consecutive rows, pair q at
-// t*T*ROWS + q*2*T + 2*tid.
-__device__ __forceinline__ int64_t fast_row(int64_t t, int T, int rows, int j) {
-    return t * (int64_t)T * rows + (int64_t)(j >> 1) * 2 * T + 2 * threadIdx.x + (j & 1);
+// Row j of this thread in the tile whose first row is `base`, shared by W
+// threads of which this is number i: pairs of consecutive rows, pair q at
+// base + q*2*W + 2*i.  (A workgroup's tile: W = blockDim.x, i = threadIdx.x,
+// base = t*W*ROWS; a wave's unit of claimed rows: W = 64, i = the lane.)
+__device__ __forceinline__ int64_t fast_row(int64_t base, int W, int i, int j) {
+    return base + (int64_t)(j >> 1) * 2 * W + 2 * i + (j & 1);
 }
 
 typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
@@ -1017,13 +1040,12 @@ __device__ __forceinline__ u64x2_t ld16(const uint64_t* p) {
 // tile of guarded single-row loads (rows >= n read as 0 and are not
 // selected), so the fused kernel covers every row in one launch.
 template <int NACC, int PRED, int ROWS, bool DERIV, int PACK, bool NUL = false>
-__device__ __forceinline__ void fast_load_tail(const GbParams& p, int64_t t,
+__device__ __forceinline__ void fast_load_tail(const GbParams& p, int64_t base, int W, int i,
                                                FastTile<NACC, ROWS, DERIV, PACK, NUL>& x) {
-    const int T = blockDim.x;
     const uint64_t* kp = (const uint64_t*)p.key.values + p.key.offset;
 #pragma unroll
     for (int j = 0; j < ROWS; ++j) {
-        const int64_t r = fast_row(t, T, ROWS, j);
+        const int64_t r = fast_row(base, W, i, j);
         const bool in = r < p.n;
         if (PACK == 2) {
             // String key: kr[0][j] = offset of row r, kr[1][j] = of row r + 1
@@ -1047,18 +1069,17 @@ __device__ __forceinline__ void fast_load_tail(const GbParams& p, int64_t t,
     }
 }
 
-// rbase: first row of tile 0 (even); rmax >= 0: row pairs beyond it are
+// base: the tile's first row (even); rmax >= 0: row pairs beyond it are
 // clamped to it (the partitioned buffers end a pair after the last row).
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
 template <int NACC, int PRED, int ROWS, bool NT, bool DERIV, int PACK, bool NUL = false>
-__device__ __forceinline__ void fast_load(const GbParams& p, int64_t t, FastTile<NACC, ROWS, DERIV, PACK, NUL>& x,
-                                          int64_t rbase = 0, int64_t rmax = -1) {
-    const int T = blockDim.x;
+__device__ __forceinline__ void fast_load(const GbParams& p, int64_t base, int W, int i,
+                                          FastTile<NACC, ROWS, DERIV, PACK, NUL>& x, int64_t rmax = -1) {
     const uint64_t* kp = (const uint64_t*)p.key.values + p.key.offset;
 #pragma unroll
     for (int q = 0; q < ROWS / 2; ++q) {
-        int64_t r = rbase + fast_row(t, T, ROWS, 2 * q);
+        int64_t r = fast_row(base, W, i, 2 * q);
         if (rmax >= 0) r = r < rmax ? r : rmax;
         if (PACK == 2) {
             // String key: the pair's offsets (16 B) and the next row's (8 B):
@@ -1157,13 +1178,12 @@ __device__ __forceinline__ uint32_t pair_word_wave(const DevCol& c, int64_t rw) 
 // 8-byte aligned bitmaps at offsets that are multiples of 64, so the
 // wave-window word and pair_bit agree.)
 template <int NACC, int PRED, int ROWS, bool PART, bool DERIV, int PACK, bool NUL>
-__device__ __forceinline__ void fast_nulls(const GbParams& p, int64_t t, FastTile<NACC, ROWS, DERIV, PACK, NUL>& x,
-                                           int64_t rbase, int64_t rmax, bool full) {
+__device__ __forceinline__ void fast_nulls(const GbParams& p, int64_t base, int W, int i,
+                                           FastTile<NACC, ROWS, DERIV, PACK, NUL>& x, int64_t rmax, bool full) {
     if constexpr (NUL) {
-        const int T = blockDim.x;
 #pragma unroll
         for (int q = 0; q < ROWS / 2; ++q) {
-            int64_t r = rbase + fast_row(t, T, ROWS, 2 * q);
+            int64_t r = fast_row(base, W, i, 2 * q);
             if (rmax >= 0) r = r < rmax ? r : rmax;
             if (PART) {
                 x.nr[q][0] = p.part_nulls ? __builtin_nontemporal_load((const uint16_t*)(p.part_nulls + r)) : 0u;
@@ -1192,18 +1212,16 @@ __device__ __forceinline__ void fast_nulls(const GbParams& p, int64_t t, FastTil
 // have landed.  A pair's bits sit at pair_bit & 31 of its word (with
 // p.vwords that is (2 lane) & 31).
 template <int NACC, int PRED, int ROWS, bool PART, bool DERIV, int PACK, bool NUL>
-__device__ __forceinline__ void fast_nulls_finish(const GbParams& p, int64_t t,
-                                                  FastTile<NACC, ROWS, DERIV, PACK, NUL>& x, int64_t rbase,
-                                                  int64_t rmax) {
+__device__ __forceinline__ void fast_nulls_finish(const GbParams& p, int64_t base, int W, int i,
+                                                  FastTile<NACC, ROWS, DERIV, PACK, NUL>& x, int64_t rmax) {
     if constexpr (NUL) {
-        const int T = blockDim.x;
 #pragma unroll
         for (int q = 0; q < ROWS / 2; ++q) {
             if (PART) {
                 x.nv[q] = x.nr[q][0];
                 continue;
             }
-            int64_t r = rbase + fast_row(t, T, ROWS, 2 * q);
+            int64_t r = fast_row(base, W, i, 2 * q);
             if (rmax >= 0) r = r < rmax ? r : rmax;
             auto bits = [&](const DevCol& c, uint32_t w) -> uint32_t {
                 return ~(w >> ((uint32_t)pair_bit(c, r) & 31u)) & 3u;
@@ -1263,6 +1281,9 @@ __device__ __forceinline__ void fast_share(const int32_t (&vf)[NACC > 0 ? NACC :
 // partition's groups.
 // Without PART the launch covers every row: the full tiles, then the rows
 // after the last full tile as one masked tile (fast_load_tail).
+// Its waves claim their rows in chunks of 64 x ROWS-row units (p.claim, below)
+// unless the launch is static (tiles strided by the grid, or the range-local
+// runs of tiles).
 // (Measured and removed variants -- no prefetch, default-policy loads,
 // 80-VGPR caps, 4 rows per thread -- are logged in DESIGN.md.)
 // DERIV: some accs are derived inputs (x op y, AccSpec.dop), computed in
@@ -1369,10 +1390,84 @@ __global__ __launch_bounds__(PART && !RUNS && ROWS == 2 ? kGbPartThreads : kGbTh
         t = blockIdx.x % p.part_blocks;
         tstep = p.part_blocks;
     }
+    // Claimed rows (p.claim, launch_fast_rows): t counts units instead of
+    // tiles -- a unit is one wave's share of a tile, 64 x ROWS rows with the
+    // lane-to-row mapping of a tile (W = 64, i = the lane), so a wave can take
+    // any unit -- and each wave claims chunks of units [t, uend) from its
+    // segment's counter: lane 0 adds to it, the wave reads the answer with
+    // readfirstlane.  The claim of the next chunk is issued with the loads of
+    // the chunk's last unit (claim_issue before load_tile), so its answer is
+    // there when those loads are: no wait of its own in the loop.  The units
+    // after n_full are the masked ones (fast_load_tail), up to a tile's worth.
+    // All of this state is wave-uniform.
+    const bool dyn = !PART && p.claim != nullptr;
+    const int W = dyn ? 64 : T;
+    const int wi = dyn ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    int64_t uend = 0;
+    int32_t seg = 0, ntaken = 0;
+    uint32_t pend = 0;
+    bool has_pend = false;
+    if (dyn) {
+        ntiles = p.n_full / (64 * ROWS);
+        nall = p.claim_units;
+        seg = (int32_t)(blockIdx.x % (uint32_t)p.claim_segs);
+    }
+    auto seg_len = [&](int64_t s_) -> int64_t {
+        const int64_t l = p.claim_units - s_ * p.claim_seg_units;
+        return l < 0 ? 0 : (l < p.claim_seg_units ? l : p.claim_seg_units);
+    };
+    // a wave stops claiming at claim_cap units (whole chunks): its workgroup's
+    // table then holds at most the rows its limbs stay exact for
+    auto claim_issue = [&]() {
+        has_pend = ntaken + p.claim_chunk <= p.claim_cap;
+        if (has_pend && (threadIdx.x & 63) == 0)
+            pend = __hip_atomic_fetch_add(p.claim + seg * kClaimStride, (uint32_t)p.claim_chunk, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_AGENT);
+    };
+    // The pending claim's chunk as [tn, uend).  A claim past its segment's end:
+    // the wave reads every counter (one per lane), moves to the segment with
+    // the most units left and claims there; false when none has any left (or
+    // at the cap).
+    auto claim_take = [&](int64_t& tn) -> bool {
+        while (has_pend) {
+            const int64_t v = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)pend);
+            const int64_t len = seg_len(seg);
+            if (v < len) {
+                tn = seg * p.claim_seg_units + v;
+                uend = seg * p.claim_seg_units + (v + p.claim_chunk < len ? v + p.claim_chunk : len);
+                ntaken += p.claim_chunk;
+                has_pend = false;
+                return true;
+            }
+            const int ln = (int)(threadIdx.x & 63);
+            uint64_t left = 0;
+            if (ln < p.claim_segs) {
+                const int64_t c = (int64_t)__hip_atomic_load(p.claim + ln * kClaimStride, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+                const int64_t l = seg_len(ln);
+                left = l > c ? (uint64_t)(l - c) : 0ull;
+            }
+            unsigned long long best = (unsigned long long)(left << 6 | (uint64_t)ln);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(best, off);
+                best = o > best ? o : best;
+            }
+            const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)best);
+            const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(best >> 32));
+            if ((((uint64_t)bhi << 32 | blo) >> 6) == 0) break;
+            seg = (int32_t)(blo & 63u);
+            claim_issue();
+        }
+        has_pend = false;
+        return false;
+    };
+    auto tile_base = [&](int64_t tt) -> int64_t { return rbase + tt * (int64_t)W * ROWS; };
     auto load_tile = [&](int64_t tt, FastTile<NL, ROWS, DERIV, PACK, NULLS>& x) {
-        fast_nulls<NL, PRED, ROWS, PART, DERIV, PACK, NULLS>(p, tt, x, rbase, rmax, tt < ntiles);
-        if (PART || tt < ntiles) fast_load<NL, PRED, ROWS, true, DERIV, PACK, NULLS>(p, tt, x, rbase, rmax);
-        else fast_load_tail<NL, PRED, ROWS, DERIV, PACK, NULLS>(p, tt, x);
+        const int64_t tb = tile_base(tt);
+        fast_nulls<NL, PRED, ROWS, PART, DERIV, PACK, NULLS>(p, tb, W, wi, x, rmax, tt < ntiles);
+        if (PART || tt < ntiles) fast_load<NL, PRED, ROWS, true, DERIV, PACK, NULLS>(p, tb, W, wi, x, rmax);
+        else fast_load_tail<NL, PRED, ROWS, DERIV, PACK, NULLS>(p, tb, W, wi, x);
     };
     // NULLS: the null bit of the predicate's column (its acc's, or its own)
     const int pbit = p.pred_acc >= 0 ? p.pred_acc : 7;
@@ -1528,10 +1623,16 @@ __global__ __launch_bounds__(PART && !RUNS && ROWS == 2 ? kGbPartThreads : kGbTh
         return true;
     };
     FastTile<NL, ROWS, DERIV, PACK, NULLS> cur;
-    if (t < nall) load_tile(t, cur);
-    for (; t < nall; t += tstep) {
+    bool have = t < nall;
+    if (dyn) {
+        claim_issue();
+        have = claim_take(t);
+        if (have && t + 1 == uend) claim_issue();
+    }
+    if (have) load_tile(t, cur);
+    while (have) {
         if constexpr (!VAR) fast_share<NACC, ROWS, DERIV, PACK, NULLS>(vf0, wf0, cur);
-        fast_nulls_finish<NL, PRED, ROWS, PART, DERIV, PACK, NULLS>(p, t, cur, rbase, rmax);
+        fast_nulls_finish<NL, PRED, ROWS, PART, DERIV, PACK, NULLS>(p, tile_base(t), W, wi, cur, rmax);
         bool kout[ROWS];
         constexpr bool kstr = PACK == 2;
         if (kstr) {
@@ -1613,10 +1714,10 @@ __global__ __launch_bounds__(PART && !RUNS && ROWS == 2 ? kGbPartThreads : kGbTh
                 if (NULLS) sel = sel && !((nrw[j] >> pbit) & 1u);
             }
             if (PART) {
-                const int64_t r = rbase + fast_row(t, T, ROWS, j);
+                const int64_t r = fast_row(tile_base(t), W, wi, j);
                 sel = r >= rlo && r < rhi;
             } else if (t >= ntiles) {
-                sel = sel && fast_row(t, T, ROWS, j) < p.n;
+                sel = sel && fast_row(tile_base(t), W, wi, j) < p.n;
             }
             if (PACK && sel && kout[j]) d.kbad = 1u;
             const bool knull = (NULLS && ((nrw[j] >> 6) & 1u)) ||
@@ -1630,12 +1731,18 @@ __global__ __launch_bounds__(PART && !RUNS && ROWS == 2 ? kGbPartThreads : kGbTh
             if (slot[j] == kGlobalKey && probe[j] == cur.key[j]) slot[j] = (int)h[j];
         // ---- next tile's loads go out before this tile's atomics
         FastTile<NL, ROWS, DERIV, PACK, NULLS> nxt;
-        const int64_t tn = t + tstep;
-        if (tn < nall) load_tile(tn, nxt);
+        int64_t tn = t + tstep;
+        bool hn = tn < nall;
+        if (dyn) {
+            tn = t + 1;
+            hn = tn < uend || claim_take(tn);
+            if (hn && tn + 1 == uend) claim_issue();
+        }
+        if (hn) load_tile(tn, nxt);
         // ---- apply rows one at a time (rolled; arrays shift statically)
 #pragma unroll 1
         for (int j = 0; j < ROWS; ++j) {
-            const int64_t r = rbase + fast_row(t, T, ROWS, j);
+            const int64_t r = fast_row(tile_base(t), W, wi, j);
             int s = slot[0];
             if (s != kNotSelected) {
                 ++d.nsel;
@@ -1784,6 +1891,8 @@ __global__ __launch_bounds__(PART && !RUNS && ROWS == 2 ? kGbPartThreads : kGbTh
             }
         }
         cur = nxt;
+        t = tn;
+        have = hn;
     }
     if (RACC) {
 #pragma unroll
@@ -1982,21 +2091,59 @@ hipError_t launch_fast_rows(const Plan& pl, const DevProgram& dp, hipStream_t s)
     // the plan's n_full is a multiple of the 2-row tile; a wider tile takes
     // its own multiple (the masked last tile covers the rest)
     if (ROWS != 2) q.n_full = (pl.p.n / ((int64_t)kGbThreads * ROWS)) * kGbThreads * ROWS;
-    // up to kGridRounds rounds of the workgroups resident per CU (later
-    // rounds' table init / flush overlap earlier rounds' streaming), but at
-    // least kMinTilesPerWg tiles per workgroup: every workgroup flushes its
-    // table to the global one, a fixed cost a short input cannot amortise
-    // (1e8 rows: 0.66 ms in one round against 0.84 ms in 8,
-    // profiles/r04_grid_rounds_ab.txt)
-    const int64_t need = (q.n_full + kMaxRowsPerWg - 1) / kMaxRowsPerWg;
+    // Every workgroup pays a fixed cost: its table's init, one HBM round
+    // trip before its first rows, and the flush of its table into the global
+    // one (1e8 rows: 0.66 ms in one round of the resident workgroups against
+    // 0.84 ms in 8, profiles/r04_grid_rounds_ab.txt).
+    // Claimed rows (the default): exactly the resident workgroups, whose waves
+    // claim their rows chunk by chunk (GbParams::claim), so fast and slow
+    // workgroups even out without more workgroups than fit.
+    // The static grid (an explicit grid_rounds, gb_claim 0, the range-local
+    // mode): tiles strided by the grid; balance comes only from the
+    // dispatcher handing out fresh workgroups, so up to kGridRounds rounds of
+    // the resident ones, but at least kMinTilesPerWg tiles per workgroup.
     const int64_t useful = q.n_full / ((int64_t)kGbThreads * ROWS);
     const int64_t resident = (int64_t)num_cus() * resident_per_cu(kern, kGbThreads, lds);
-    const int64_t rounds = options().grid_rounds > 0
-                               ? options().grid_rounds
-                               : std::min<int64_t>(kGridRounds, std::max<int64_t>(1, useful / (resident * kMinTilesPerWg)));
-    int64_t g = resident * rounds;
-    if (g < need) g = need;
-    if (g > useful) g = std::max<int64_t>(1, useful);
+    const bool claimable = !pl.local && options().grid_rounds == 0;
+    const bool claimed = claimable && options().gb_claim != 0 && q.claim != nullptr;
+    int64_t g;
+    if (claimed) {
+        constexpr int64_t unit = 64 * ROWS, waves = kGbThreads / 64;
+        const int64_t cap_rows =
+            options().claim_cap_rows > 0 ? std::min<int64_t>(options().claim_cap_rows, kMaxRowsPerWg) : kMaxRowsPerWg;
+        int64_t cap = std::max<int64_t>(1, cap_rows / (waves * unit));  // units per wave
+        const int64_t units = q.n_full / unit + (pl.p.n - q.n_full + unit - 1) / unit;
+        // kClaimChunk units per claim; fewer on a short input, so that every
+        // resident wave still finds some chunks to take
+        const int64_t chunk = std::min<int64_t>(
+            cap, std::max<int64_t>(1, std::min<int64_t>(kClaimChunk, units / (resident * waves * 4))));
+        cap -= cap % chunk;
+        q.claim_segs = kClaimSegs;
+        q.claim_chunk = (int32_t)chunk;
+        q.claim_cap = (int32_t)cap;
+        // whole chunks per segment: only the launch's last chunk is short
+        q.claim_seg_units = ((units + kClaimSegs - 1) / kClaimSegs + chunk - 1) / chunk * chunk;
+        q.claim_units = units;
+        // Invariant: grid x waves x cap >= the units rounded up to whole
+        // chunks.  A wave stops only at its cap (cap / chunk claims that
+        // succeeded) or when no segment has a unit left; were a unit left
+        // with every wave stopped, every wave would be at its cap and the
+        // claims made would cover all the chunks.  So no unit stays unclaimed,
+        // and a workgroup's table sees at most waves x cap units: cap_rows.
+        const int64_t need = ((units + chunk - 1) / chunk * chunk + waves * cap - 1) / (waves * cap);
+        g = std::min<int64_t>(resident, std::max<int64_t>(1, useful));
+        if (g < need) g = need;
+    } else {
+        q.claim = nullptr;
+        const int64_t need = (q.n_full + kMaxRowsPerWg - 1) / kMaxRowsPerWg;
+        const int64_t rounds =
+            options().grid_rounds > 0
+                ? options().grid_rounds
+                : std::min<int64_t>(kGridRounds, std::max<int64_t>(1, useful / (resident * kMinTilesPerWg)));
+        g = resident * rounds;
+        if (g < need) g = need;
+        if (g > useful) g = std::max<int64_t>(1, useful);
+    }
     const int grid = (int)g;
     pl.launched_grid = grid;
     pl.launched_runs = RUNS;
@@ -2010,8 +2157,10 @@ hipError_t launch_fast_rows(const Plan& pl, const DevProgram& dp, hipStream_t s)
         const int64_t nall = q.n_full / tile + (pl.p.n > q.n_full ? 1 : 0);
         q.tiles_per_wg = (int32_t)((nall + grid - 1) / grid);
     }
-    // (option wave_report: a timer name of its own, the tests' proof that it ran)
-    KtScope kt(q.wave_report ? "gb_fast_wave_report_kernel" : "gb_fast_kernel", s);
+    // (options wave_report, and gb_claim 0 where rows would have been
+    // claimed: timer names of their own, the tests' proof of what ran)
+    KtScope kt(q.wave_report ? "gb_fast_wave_report_kernel"
+                             : (claimable && !claimed ? "gb_fast_static_kernel" : "gb_fast_kernel"), s);
     gb_fast_kernel<NACC, PRED, SUMONLY, ROWS, LIMBS, RUNS, false, DERIV, VAR, PACK, NULLS>
         <<<grid, kGbThreads, lds, s>>>(q, dp);
     return hipGetLastError();

@@ -45,6 +45,12 @@ struct Options {
     int fuse_keys = 1;   // 0: packed multi-key codes go through a code column (tests / A-B)
     int plan_cache = 1;  // 0: every group-by samples its inputs (no reuse of recent plan statistics)
     int grid_rounds = 0; // fused group-by grid in rounds of resident workgroups (0: kGridRounds; A-B)
+    // fused group-by without an explicit grid_rounds: 1 the resident workgroups' waves claim their rows
+    // chunk by chunk, 0 the static grid of up to kGridRounds rounds (A/B)
+    int gb_claim = 1;
+    // claimed rows: rows per workgroup at which its waves stop claiming, a multiple of 1024
+    // (0: kMaxRowsPerWg; tests reach the cap with a small input)
+    int claim_cap_rows = 0;
     // group-by path hooks (tests: the forced-path parity sweep, DESIGN.md
     // "Group-by paths"): -1 lets the plan choose
     int gb_path = -1;     // 0 generic kernel on the global table, 1 generic with LDS tables,

@@ -89,6 +89,8 @@ const OptField kOptFields[] = {
     {"join_radix_load", "PLGPU_JOIN_RADIX_LOAD", &Options::join_radix_load},
     {"join_radix_batch", "PLGPU_JOIN_RADIX_BATCH", &Options::join_radix_batch},
     {"asof_path", "PLGPU_ASOF_PATH", &Options::asof_path},
+    {"gb_claim", "PLGPU_GB_CLAIM", &Options::gb_claim},
+    {"claim_cap_rows", "PLGPU_CLAIM_CAP_ROWS", &Options::claim_cap_rows},
 };
 const OptField* opt_field(const char* name) {
     for (const OptField& f : kOptFields)
