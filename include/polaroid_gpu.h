@@ -1074,6 +1074,57 @@ int plgpu_join_asof(const plgpu_column* left_on, const plgpu_column* right_on,
                     plgpu_column* out_idx, int32_t* out_path, void* stream);
 int plgpu_is_sorted_asc(const plgpu_column* col, int32_t* out_ascending, int32_t* out_nulls_first, void* stream);
 
+/* ---- quantile ---------------------------------------------------------------------
+ * plgpu_segment_quantile: nq quantiles of every segment of a column that is
+ * sorted within its segments: median / quantile, plain, per group and over
+ * keys.  The caller has sorted by (group, value) with the value's nulls last
+ * (plgpu_arg_sort_multi), gathered, and marked the segment starts of the
+ * gathered groups (plgpu_segment_starts).  Replaces
+ * polars-core/src/chunked_array/ops/aggregate/quantile.rs:106 generic_quantile
+ * (:16 quantile_idx, :46 linear_interpol, :54 midpoint_interpol) and over groups
+ * polars-core/src/frame/group_by/aggregations/mod.rs:251 agg_quantile_generic.
+ *   sorted_values  Int32 / Int64 / UInt32 / Float64; within every segment
+ *                  ascending in TotalOrd (NaN greatest) with its nulls last.
+ *   seg_starts     NULL: one segment (also of an empty column: one null row);
+ *                  else null-free Boolean, n rows; row 0 starts a segment
+ *                  whatever its bit says.  With n == 0 the outputs have no rows.
+ *   quantiles      nq values in [0, 1].
+ *   methods        nq values of plgpu_quantile_method.
+ *   outs           nq owned Float64 columns, one row per segment in segment
+ *                  order.  They carry a validity buffer only when some segment
+ *                  holds no non-null value; such a row is null and its bytes
+ *                  are zero.
+ * For a segment of len rows, nc of them null, nn = len - nc > 0, in f64:
+ *   float_idx = (nn - 1.0) * q + (double)nc
+ *   NEAREST       idx = round(float_idx), halves away from zero
+ *   EQUIPROBABLE  idx = max(ceil(nn * q) - 1.0, 0.0) + nc
+ *   LOWER / MIDPOINT / LINEAR  idx = min((size_t)float_idx, len - 1)
+ *   HIGHER        idx = min((size_t)ceil(float_idx), len - 1)
+ * idx counts the segment's rows with its nulls first, so the row read is
+ * start + (idx - nc); lower = (double)sorted[idx] is the result, except that
+ * MIDPOINT and LINEAR with ceil(float_idx) != idx take upper = (double)sorted[idx + 1]
+ * and give, when lower != upper (IEEE), (lower + upper) / 2.0 and
+ * (float_idx - (double)idx) * (upper - lower) + lower.
+ * Every input may be sliced and its bitmap unaligned.
+ * PLGPU_ERR_INVALID: a NULL argument (seg_starts apart), nq outside 1..8, a
+ * quantile outside [0, 1] or NaN, an unknown method, another dtype, a
+ * seg_starts that is not a null-free Boolean column of the values' length, more
+ * than 2^32 - 1 rows; all before any device work.
+ * Four launches (segment starts per tile, scan of the tile counts, the starts
+ * as row ids, one lane per segment), one device-to-host copy of the segment
+ * count between them; no workgroup waits on another. */
+enum plgpu_quantile_method {
+    PLGPU_QUANTILE_NEAREST = 1,
+    PLGPU_QUANTILE_HIGHER = 2,
+    PLGPU_QUANTILE_LOWER = 3,
+    PLGPU_QUANTILE_MIDPOINT = 4,
+    PLGPU_QUANTILE_LINEAR = 5,
+    PLGPU_QUANTILE_EQUIPROBABLE = 6
+};
+int plgpu_segment_quantile(const plgpu_column* sorted_values, const plgpu_column* seg_starts /* NULL: one segment */,
+                           const double* quantiles, const int32_t* methods, int32_t nq, plgpu_column* outs,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

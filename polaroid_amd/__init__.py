@@ -23,7 +23,7 @@ from ._native import (
     ShapeError,
     device_count,
 )
-from .expr import Expr, col, count, first, last, len, lit, max, mean, min, sum, when
+from .expr import Expr, col, count, first, last, len, lit, max, mean, median, min, quantile, sum, when
 from .frame import (
     Boolean,
     DataFrame,
@@ -54,7 +54,7 @@ __all__ = [
     "Duration", "Expr", "Float32", "Float64", "GroupBy", "Int8", "Int16", "Int32", "Int64",
     "InvalidOperationError", "LazyFrame", "LazyGroupBy", "OutOfMemoryError", "PolaroidError", "Series",
     "ShapeError", "String", "UInt8", "UInt16", "UInt32", "UInt64", "col", "count", "device_count", "from_dict",
-    "first", "last", "len", "lit", "max", "mean", "min", "sum", "when",
+    "first", "last", "len", "lit", "max", "mean", "median", "min", "quantile", "sum", "when",
 ]
 
 

@@ -217,6 +217,8 @@ SIGNATURES = {
     "plgpu_join_asof": (C.c_int, [_COLP, _COLP, _COLP, _COLP, _COLP, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                   C.c_double, _COLP, C.POINTER(C.c_int32), _P]),
     "plgpu_is_sorted_asc": (C.c_int, [_COLP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "plgpu_segment_quantile": (C.c_int, [_COLP, _COLP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, _COLP,
+                                         _P]),
 }
 
 GB_MAX_ACC = 6
@@ -228,6 +230,10 @@ CUM = {"sum": 1, "min": 2, "max": 3, "count": 4}
 LAG = {"shift": 1, "diff": 2}
 FILL = {"forward": 1, "backward": 2}
 RANK = {"average": 1, "min": 2, "max": 3, "dense": 4, "ordinal": 5}
+QUANTILE = {"nearest": 1, "higher": 2, "lower": 3, "midpoint": 4, "linear": 5, "equiprobable": 6}
+(QUANTILE_NEAREST, QUANTILE_HIGHER, QUANTILE_LOWER, QUANTILE_MIDPOINT, QUANTILE_LINEAR,
+ QUANTILE_EQUIPROBABLE) = range(1, 7)
+QUANTILE_MAX = 8            # kQuantileMax (csrc/quantile.hip): quantiles of one plgpu_segment_quantile call
 ASOF = {"backward": 0, "forward": 1, "nearest": 2}
 ASOF_PATH = {1: "staged", 2: "global", 3: "ranged"}  # plgpu_join_asof's *out_path
 # The geometry of the as-of join's window search (csrc/asof.hip)

@@ -644,6 +644,13 @@ def group_by_agg(df, key: str, aggs: Sequence[Expr], predicate: Expr | None = No
         aggregate them there with the single-GPU group-by."""
     import torch.distributed as dist
 
+    from .frame import _is_quantile
+
+    for e in aggs:
+        if _is_quantile(e):
+            raise N.InvalidOperationError(
+                f"{e!r}: median / quantile are not supported by the multi-GPU group-by (a group's quantile needs "
+                "all of its rows on one GPU; no partial state merges)")
     if not dist.is_initialized():
         raise N.InvalidOperationError("torch.distributed is not initialised")
     device = _device_for(group)

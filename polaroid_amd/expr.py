@@ -93,6 +93,8 @@ class Expr:
             return f"{self.args[0]!r}.cast({self.value!r}, {self.op})"
         if self.kind == "fill_null":
             return f"{self.args[0]!r}.fill_null({self.args[1]!r})"
+        if self.kind == "agg" and self.op == "quantile":
+            return f"{self.args[0]!r}.quantile({self.value[0]!r}, interpolation={self.value[1]!r})"
         return f"{self.args[0]!r}.{self.op}()"
 
     def __bool__(self):
@@ -249,6 +251,17 @@ class Expr:
     def first(self): return self._agg("first")
     def last(self): return self._agg("last")
 
+    def median(self) -> "Expr":
+        """Expr.median: quantile(0.5, "linear") (polars-core/src/chunked_array/ops/aggregate/quantile.rs:168)."""
+        return self._agg("median", (0.5, "linear"))
+
+    def quantile(self, quantile: Any, interpolation: str = "nearest") -> "Expr":
+        """Expr.quantile with a literal `quantile` in [0, 1]: nearest / higher /
+        lower / midpoint / linear / equiprobable (quantile.rs:106
+        generic_quantile).  Float32 stays Float32, every other numeric dtype
+        gives Float64."""
+        return self._agg("quantile", (_quantile_q(quantile), _quantile_method(interpolation)))
+
     # ------------------------------------------------- window / ordering
     def rolling_sum(self, window_size: int, weights=None, *, min_samples: int | None = None,
                     center: bool = False) -> "Expr":
@@ -358,7 +371,7 @@ class Expr:
         keys, each result back at its row (polars-expr/src/expressions/
         window.rs:356 WindowExpr::evaluate with WindowMapping::GroupsToRows).
         Takes `<elementwise>.rolling_*(...)`, the aggregations sum / mean /
-        min / max / count / len / first / last / std / var of an elementwise
+        min / max / count / len / first / last / std / var / median / quantile of an elementwise
         expression (or pl.len()), and `<elementwise>.cum_*()` / `.shift(...)` /
         `.diff(...)` / `.forward_fill(...)` / `.backward_fill(...)` /
         `.fill_null(strategy=...)` / `.ewm_mean(...)` / `.rank(...)`, over
@@ -557,6 +570,33 @@ def _prepare_alpha(com: Any = None, span: Any = None, half_life: Any = None, alp
     return float(alpha)
 
 
+_QUANTILE_METHODS = ("nearest", "higher", "lower", "midpoint", "linear", "equiprobable")
+
+
+def _quantile_method(method: Any) -> str:
+    if not isinstance(method, builtins.str) or method not in _QUANTILE_METHODS:
+        raise ValueError(f"quantile: `interpolation` must be one of {', '.join(map(repr, _QUANTILE_METHODS))}, "
+                         f"got {method!r}")
+    return method
+
+
+def _quantile_q(q: Any) -> float:
+    """A literal `quantile`: a Python or NumPy real number in [0, 1]."""
+    import numbers
+
+    if isinstance(q, Expr) and q.kind == "lit":
+        q = q.value
+    if isinstance(q, Expr):
+        raise N.InvalidOperationError(
+            f"quantile({q!r}): a computed `quantile` is not supported on the GPU executor (pass a number)")
+    if isinstance(q, bool) or not isinstance(q, numbers.Real):
+        raise N.InvalidOperationError(f"quantile({q!r}): `quantile` must be a real number")
+    q = float(q)
+    if not 0.0 <= q <= 1.0:  # NaN fails both comparisons
+        raise N.ComputeError("`quantile` should be between 0.0 and 1.0")
+    return q
+
+
 _RANK_METHODS = ("average", "min", "max", "dense", "ordinal")
 
 
@@ -587,7 +627,7 @@ def _ewm_min_samples(v: Any) -> int:
     return v
 
 
-_OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var")
+_OVER_AGGS = ("sum", "mean", "min", "max", "count", "len", "first", "last", "std", "var", "median", "quantile")
 # the segmented scans (frame._window_fn; csrc/seg_scan.hpp); rank follows their rules everywhere
 _SCAN_KINDS = ("cum", "lag", "fill", "ewm", "rank")
 _ELEMENTWISE = ("col", "lit", "bin", "un", "alias", "ternary", "cast", "fill_null", "strfn", "over")
@@ -686,6 +726,14 @@ def first(name: str) -> Expr:
 
 def last(name: str) -> Expr:
     return col(name).last()
+
+
+def median(name: str) -> Expr:
+    return col(name).median()
+
+
+def quantile(name: str, quantile: Any, interpolation: str = "nearest") -> Expr:
+    return col(name).quantile(quantile, interpolation)
 
 
 class _StrNamespace:

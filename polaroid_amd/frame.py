@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _native as N
 from .expr import (_SCAN_KINDS, Expr, _ewm_min_samples, _fill_args, _fill_limit, _has_over, _has_scan, _lag_n,
-                   _prepare_alpha, _rank_method, col, lit, lower, to_instr_array)
+                   _prepare_alpha, _quantile_method, _quantile_q, _rank_method, col, lit, lower, to_instr_array)
 
 
 # ------------------------------------------------------------------ dtypes
@@ -897,6 +897,79 @@ class Series:
     def rank(self, method: str = "average", *, descending: bool = False, seed: int | None = None) -> "Series":
         return self._rank(method, descending)
 
+    # median / quantile (Series.median, Series.quantile) ------------------------
+    def _quantile(self, qs: Sequence[float], methods: Sequence[str],
+                  keys: "Sequence[Series] | None" = None) -> "list[Series]":
+        """The quantiles (qs[i], methods[i]) of this column on the device
+        (quantile.rs:106 generic_quantile): one stable sort with the nulls
+        last, a gather, then plgpu_segment_quantile, all pairs in one call (at
+        most N.QUANTILE_MAX each).  `keys` (group ids, or the partition keys as
+        _over_sort_keys gives them): the sort is by the keys first and every
+        run of equal key tuples is a segment, so the results have one row per
+        key tuple in ascending key order; without keys one row.  The casts are
+        rank's: Int8 / Int16 / UInt8 / UInt16 as Int64, Float32 as Float64
+        (the result is rounded once to Float32); everything else gives
+        Float64."""
+        qs = [_quantile_q(q) for q in qs]
+        methods = [_quantile_method(m) for m in methods]
+        if self._cat_codes() is not None or self.dtype is String or self.dtype is Boolean:
+            raise N.InvalidOperationError(
+                f"median / quantile of a {self.dtype} column is not supported on the GPU executor (it takes "
+                "numeric columns)")
+        if self._logical_dtype() is not None:
+            raise N.InvalidOperationError(
+                f"median / quantile of a {self.dtype} column is not supported on the GPU executor yet: Date, "
+                "Datetime, Duration and Time medians are a follow-up")
+        phys = _BY_CODE[self._col.dtype]
+        if phys in (Int8, Int16, UInt8, UInt16):
+            src = self._cast_to(Int64)
+        elif phys is Float32:
+            src = self._cast_to(Float64)
+        elif phys in (Int32, Int64, UInt32, Float64):
+            src = self
+        else:
+            raise N.InvalidOperationError(
+                f"median / quantile of a {self.dtype} column is not supported on the GPU executor (the sort takes "
+                "Int32, Int64, UInt32 and Float64 values; UInt64 is not among them)")
+        cols = list(keys or []) + [src]
+        k = builtins.len(cols)
+        if k > N.MAX_KEYS:
+            raise N.InvalidOperationError(
+                f"median / quantile over {k - 1} keys is not supported on the GPU executor: the sort takes "
+                f"{N.MAX_KEYS} columns and the value is one of them")
+        if builtins.any(c.len() != src.len() for c in cols):
+            raise N.ShapeError("quantile: the keys and the values differ in length")
+        idx = N.Column()
+        if k == 1:
+            N.check(N.lib().plgpu_arg_sort(C.byref(src._col), 0, 1, C.byref(idx), None))
+        else:  # keys ascending with their nulls first; the value ascending, its nulls last
+            zeros = (C.c_int32 * k)(*([0] * k))
+            last = (C.c_int32 * k)(*([0] * (k - 1) + [1]))
+            N.check(N.lib().plgpu_arg_sort_multi(_col_array(cols), k, zeros, last, C.byref(idx), None))
+        idx_s = Series._from_native("__idx", idx)
+        got = (N.Column * k)()
+        N.check(N.lib().plgpu_gather(_col_array(cols), k, C.byref(idx_s._col), got, None))
+        srt = [Series._from_native(c.name, got[i]) for i, c in enumerate(cols)]
+        seg = _segment_starts(srt[:-1])[0] if k > 1 else None
+        res: list[Series] = []
+        for at in range(0, builtins.len(qs), N.QUANTILE_MAX):
+            qc, mc = qs[at:at + N.QUANTILE_MAX], methods[at:at + N.QUANTILE_MAX]
+            nq = builtins.len(qc)
+            outs = (N.Column * nq)()
+            N.check(N.lib().plgpu_segment_quantile(
+                C.byref(srt[-1]._col), None if seg is None else C.byref(seg._col), (C.c_double * nq)(*qc),
+                (C.c_int32 * nq)(*[N.QUANTILE[m] for m in mc]), nq, outs, None))
+            res += [Series._from_native(self.name, outs[i]) for i in range(nq)]
+        if phys is Float32:
+            res = [r._cast_to(Float32) for r in res]
+        return res
+
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> "float | None":
+        return self._quantile([quantile], [interpolation])[0].to_list()[0]
+
+    def median(self) -> "float | None":
+        return self._quantile([0.5], ["linear"])[0].to_list()[0]
+
     def _physical_view(self) -> "Series":
         """This column without its logical dtype (the same buffers)."""
         s = self.alias(self.name)
@@ -1247,6 +1320,12 @@ class DataFrame:
     def with_columns(self, *exprs: Any) -> "DataFrame":
         return self.lazy().with_columns(*exprs).collect()
 
+    def median(self) -> "DataFrame":
+        return self.lazy().median().collect()
+
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> "DataFrame":
+        return self.lazy().quantile(quantile, interpolation).collect()
+
     def __repr__(self) -> str:
         return f"DataFrame(shape={self.shape}, schema={self.schema})"
 
@@ -1404,6 +1483,14 @@ class LazyFrame:
     def with_columns(self, *exprs: Any) -> "LazyFrame":
         return LazyFrame(("with_columns", self._node, _parse_exprs(exprs)))
 
+    def median(self) -> "LazyFrame":
+        """The median of every column, one row (a non-numeric column is refused by name)."""
+        return LazyFrame(("select", self._node, _EveryColumn(0.5, "linear", True)))
+
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> "LazyFrame":
+        """The quantile of every column, one row (a non-numeric column is refused by name)."""
+        return LazyFrame(("select", self._node, _EveryColumn(quantile, interpolation)))
+
     def collect(self, engine: str = "gpu", info: dict | None = None) -> DataFrame:
         """Execute on the GPU.  `engine` is accepted for API parity with
         polars' `collect(engine=...)`; every node runs on the HIP executor."""
@@ -1422,6 +1509,22 @@ def _join_keys(on: Any) -> str | tuple:
         raise N.InvalidOperationError("the GPU executor joins on at most 8 key columns")
     names = [k.value for k in keys]
     return names[0] if builtins.len(names) == 1 else tuple(names)
+
+
+class _EveryColumn:
+    """The aggregation list of the median() / quantile() shorthands: the
+    quantile of every column that is not a key, resolved against the frame
+    when the plan runs (a lazy plan does not know its columns before)."""
+
+    def __init__(self, quantile: Any, interpolation: str, median: bool = False):
+        self.q, self.method, self.median = _quantile_q(quantile), _quantile_method(interpolation), median
+
+    def resolve(self, df: "DataFrame", keys: Sequence[str]) -> list[Expr]:
+        cols = [c for c in df.columns if c not in keys]
+        return [col(c).median() if self.median else col(c).quantile(self.q, self.method) for c in cols]
+
+    def __repr__(self) -> str:
+        return "[*.median()]" if self.median else f"[*.quantile({self.q!r}, interpolation={self.method!r})]"
 
 
 class LazyGroupBy:
@@ -1444,6 +1547,15 @@ class LazyGroupBy:
         from .expr import len as len_expr
         return self.agg(len_expr().alias(name))
 
+    def median(self) -> LazyFrame:
+        """The median of every column that is not a key (a non-numeric one is refused by name)."""
+        return LazyFrame(("group_by", self._lf._node, self._key, _EveryColumn(0.5, "linear", True), self._maintain))
+
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> LazyFrame:
+        """The quantile of every column that is not a key (a non-numeric one is refused by name)."""
+        return LazyFrame(("group_by", self._lf._node, self._key, _EveryColumn(quantile, interpolation),
+                          self._maintain))
+
 
 class GroupBy:
     """Eager DataFrame.group_by: runs the lazy plan (as py-polars does)."""
@@ -1456,6 +1568,12 @@ class GroupBy:
 
     def len(self, name: str = "len") -> DataFrame:
         return self._g.len(name).collect()
+
+    def median(self) -> DataFrame:
+        return self._g.median().collect()
+
+    def quantile(self, quantile: float, interpolation: str = "nearest") -> DataFrame:
+        return self._g.quantile(quantile, interpolation).collect()
 
 
 # ----------------------------------------------------------------- planner
@@ -2340,8 +2458,79 @@ def _group_by_var(df: DataFrame, key: str | tuple, aggs: list[Expr], maintain_or
     return DataFrame(out + [res[i] for i in range(builtins.len(aggs))])
 
 
+def _is_quantile(e: Expr) -> bool:
+    b = _agg_base(e)
+    return b.kind == "agg" and b.op in ("median", "quantile")
+
+
+def _group_by_quantile(df: DataFrame, key: str | tuple | None, aggs: list[Expr], maintain_order: bool,
+                       pred: Expr | None, info: dict | None) -> DataFrame:
+    """group_by().agg() with median / quantile (polars-core/src/frame/group_by/
+    aggregations/mod.rs:251 agg_quantile_generic), composed of GPU passes
+    that do not depend on the kinds or the number of the keys:
+      1. the group-by of the other aggregations (len() alone when there are
+         none) in first-occurrence order: its rows are the output's;
+      2. its rows numbered 0..G-1, and the frame's key columns left-joined to
+         them with nulls equal (as _over_agg does): every row's group id;
+      3. per distinct input expression one evaluation, one sort by (group
+         id, value) with the value's nulls last, one gather and one
+         plgpu_segment_quantile call with all of that input's (q, method)
+         pairs (Series._quantile): segment g is output row g.
+    A filter below is materialised first.  `key` None (select(aggregations))
+    is one segment: no ids and no join.  info["quantile_sorts"] counts the
+    sorts of step 3."""
+    from .expr import len as len_expr
+
+    if pred is not None:
+        df, pred = _filter(df, pred), None
+    keys = _gb_keys(key)
+    for k in keys:
+        if k not in df._cols:
+            raise N.ComputeError(f'unable to find column "{k}"')
+    others = [e for e in aggs if not _is_quantile(e)]
+    base = _group_by(df, key, others or [len_expr().alias("__q_len")], True, None, info)
+    gid = None
+    if keys:
+        like = next((s for s in base._cols.values() if s._cat_codes() is None and s.dtype is not String
+                     and s.dtype is not Boolean), None)
+        if like is None:
+            like = _group_by(df, key, [len_expr().alias("__q_len")], True, None, None)["__q_len"]
+        ids = _row_ids(like).alias("__q_gid")
+
+        def plain(s: Series) -> Series:  # a Categorical joins on its codes, as it is grouped
+            cc = s._cat_codes()
+            return s if cc is None else cc[1].alias(s.name)
+        left = DataFrame([plain(df._cols[k]) for k in keys])
+        right = DataFrame([plain(base._cols[k]) for k in keys] + [ids])
+        gid = _join(left, right, key, key, "_right", "m:m", True, "left", "left", None)["__q_gid"]
+    # the quantiles of one input share its sort
+    inputs: dict[str, list[int]] = {}
+    for i, e in enumerate(aggs):
+        if _is_quantile(e):
+            inputs.setdefault(repr(_agg_base(e).args[0]), []).append(i)
+    res: dict[int, Series] = {}
+    for idxs in inputs.values():
+        x = _agg_base(aggs[idxs[0]]).args[0]
+        if not x.meta_root_names():
+            raise N.InvalidOperationError(
+                f"aggregation {aggs[idxs[0]]!r} of a literal is not supported on the GPU executor")
+        vals = _eval(x, df)
+        if vals.len() != df.height:
+            raise N.ShapeError("quantile: the keys and the values differ in length")
+        pairs = [_agg_base(aggs[i]).value for i in idxs]
+        got = vals._quantile([p[0] for p in pairs], [p[1] for p in pairs], None if gid is None else [gid])
+        if info is not None:
+            info["quantile_sorts"] = info.get("quantile_sorts", 0) + 1
+        for i, s in zip(idxs, got):
+            res[i] = s.alias(aggs[i].output_name())
+    return DataFrame([base._cols[k] for k in keys]
+                     + [res[i] if i in res else base._cols[e.output_name()] for i, e in enumerate(aggs)])
+
+
 def _group_by(df: DataFrame, key: str | tuple, aggs: list[Expr], maintain_order: bool,
               pred: Expr | None, info: dict | None) -> DataFrame:
+    if any(_is_quantile(e) for e in aggs):
+        return _group_by_quantile(df, key, aggs, maintain_order, pred, info)
     if any(_agg_base(e).kind == "agg" and _agg_base(e).op in ("std", "var") for e in aggs):
         return _group_by_var(df, key, aggs, maintain_order, pred, info)
     return _group_by_plain(df, key, aggs, maintain_order, pred, info)
@@ -2778,7 +2967,11 @@ def _execute(node: tuple, info: dict | None = None) -> DataFrame:
             pred = child[2]
             child = child[1]
         df = _execute(child, info)
-        return _group_by(df, node[2], node[3], node[4], pred, info)
+        aggs = node[3].resolve(df, _gb_keys(node[2])) if isinstance(node[3], _EveryColumn) else node[3]
+        return _group_by(df, node[2], aggs, node[4], pred, info)
+    if kind == "select" and isinstance(node[2], _EveryColumn):
+        df = _execute(node[1], info)
+        return _group_by(df, None, node[2].resolve(df, []), False, None, info)
     if kind == "select" and node[2] and builtins.all(_agg_base(e).kind in ("agg", "len") for e in node[2]):
         # select(aggregations): a global reduction (polars-expr/src/reduce/
         # sum.rs:112 reduce_ca and siblings), the fused group-by kernel with
